@@ -13,19 +13,28 @@ One "step" = one 512-sample buffer rendered by every instance of every rank.  `v
 output samples per second over all instances of all ranks (weak scaling: I per GPU fixed).
 The rendered audio stays in HBM (inputs resident, no PCIe in the timed region except the
 per-step event list and the 40-byte-per-engine status block the host state machine needs);
-`pcie_inclusive` repeats the run with every block copied to pinned host memory.
+`pcie_inclusive` (--full) repeats the run with every block copied to pinned host memory.
 
 `--workload batch` makes BASELINE configs[3] (ml/render_model_notes.py: 64 notes x 8 velocities x 5 s,
 `preamp-bench render` semantics) the headline instead: jobs dealt round-robin over the ranks, ONE
-RCCL gather of the f32 slabs to rank 0, timed separately.  Every run (any workload, any N) also
-carries a `batch` object with that literal grid and a grid scaled to 8 192 jobs per GPU, so the
-driver's 1/2/4/8-GPU runs show the batch path at both sizes.
+RCCL gather of the f32 slabs to rank 0, timed separately.  Every --full run (any workload, any N)
+also carries a `batch` object with that literal grid and a grid scaled to 8 192 jobs per GPU, so
+1/2/4/8-GPU runs show the batch path at both sizes.
 
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself, before this process
 touches the GPU; under torchrun it reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as usual.
 
-After the timed region the line verifies itself (`verified`): every row of the last block finite and inside the level band, eight
-engines spread over the pool with 64 active voices and zero NaN-guard / reset counters; a failed check exits non-zero.
+A plain run does only what the headline needs: it sets up, warms up, times --steps steps (the roofline comes from the per-kernel
+events of those steps), writes --dump-outputs if asked and prints the line.  `--full` adds everything else, after the timed region:
+the line verifies itself (`verified`: every row of the last block finite and inside the level band, eight engines spread over the
+pool with 64 active voices and zero NaN-guard / reset counters; a failed check exits non-zero), the extras (`--no-extras` drops them)
+and the CPU baseline (`--no-cpu-baseline`); `--workload batch` times its scaled grid as well.  In a plain run `verified` is null and
+the extras and `cpu_baseline` are absent or null.
+
+`--dump-outputs DIR` writes what the last timed step delivered: engines workload `audio.npy` (float32 [k, 512], the block of k engines
+of rank 0's pool) and `audio_engines.npy` (their indices), batch workload `batch_audio.npy` / `batch_jobs.npy` (k jobs of the literal
+grid); the engines / jobs are a fixed, seeded sample (dump_engine_runs, dump_sample, dump_batch_shape), so two builds run with the
+same arguments can be compared output for output.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for the roofline arithmetic.
 """
@@ -131,6 +140,12 @@ class Script:
         self.kernel_launches = 0
         self.t_midi = 0.0
         self.t_render = 0.0
+        # --dump-outputs: a step cut at an epoch boundary renders twice into the same output block, so the earlier piece is read out
+        # (by capture(length)) before the next render overwrites it; t_capture is that read's wall time, which timed_steps takes back out
+        # (the maximum over the ranks, on every rank)
+        self.capture = None
+        self.capture_from = None
+        self.t_capture = 0.0
 
     def step(self, profile=False):
         done = 0
@@ -146,6 +161,10 @@ class Script:
                 self.pool.render_into(self.host_out[0], self.host_out[1], nxt)
             self.t_midi += t1 - t0
             self.t_render += time.perf_counter() - t1
+            if self.capture is not None and done + nxt < self.buf and self.pos >= self.capture_from:
+                tc = time.perf_counter()
+                self.capture(nxt)
+                self.t_capture += time.perf_counter() - tc
             if profile:
                 ms = self.pool.last_kernel_ms()
                 self.kernel_ms += np.array([ms["ops"], ms["voices"], ms["tremolo"], ms["preamp"], ms["post"]]) * (nxt / self.buf)
@@ -332,8 +351,9 @@ class DryRunPool:
 
 
 # ---------------------------------------------------------------------------------------------------------------- batch path
-def batch_pass(jobs, sr, dur, dist, world, render_fn=None):
-    """One pass of the sharded batch render: (elapsed_s over render + gather, max over ranks; per-phase maxima; ranks the collective saw)."""
+def batch_pass(jobs, sr, dur, dist, world, render_fn=None, keep=None):
+    """One pass of the sharded batch render: (elapsed_s over render + gather, max over ranks; per-phase maxima; ranks the collective saw).
+    keep (dict): receives the pass's result under "slabs" (rank 0: the gathered per-rank slabs, job j = row j // world of slab j % world)."""
     import torch
     from openwurli_amd import distributed as owd
     tm = {}
@@ -348,26 +368,30 @@ def batch_pass(jobs, sr, dur, dist, world, render_fn=None):
         t = torch.tensor(vals, dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         vals = [float(x) for x in t.tolist()]
+    if keep is not None:
+        keep["slabs"] = res
     del res
     return vals[0], vals[1], vals[2], tm["world_seen"]
 
 
-def batch_bench(dist, world, steps, warmup, scaled_jobs_per_gpu=8192, scaled_dur=1.0, render_fn=None, literal_dur=5.0):
+def batch_bench(dist, world, steps, warmup, scaled_jobs_per_gpu=8192, scaled_dur=1.0, render_fn=None, literal_dur=5.0,
+                grids=("literal", "scaled"), keep=None):
     """configs[3] literal (512 jobs x 5 s: 8 + 64 wavefronts, latency-bound, cannot scale) and a grid scaled until every GPU holds
-    `scaled_jobs_per_gpu` jobs (the regime in which >= 6x at 8 GPUs is reachable)."""
+    `scaled_jobs_per_gpu` jobs (the regime in which >= 6x at 8 GPUs is reachable).  keep: see batch_pass (the last pass of the literal grid)."""
     from openwurli_amd.distributed import model_notes_job_list
     out = {}
     base = model_notes_job_list()
-    grids = {"literal": (base, literal_dur),
-             "scaled": ([base[i % len(base)] for i in range(scaled_jobs_per_gpu * world)], scaled_dur)}
+    grids = {name: g for name, g in (("literal", (base, literal_dur)),
+                                     ("scaled", ([base[i % len(base)] for i in range(scaled_jobs_per_gpu * world)], scaled_dur)))
+             if name in grids}
     for name, (jobs, dur) in grids.items():
         n = int(dur * SR)
         for _ in range(warmup):
             batch_pass(jobs, SR, dur, dist, world, render_fn)
         el = rs = gs = 0.0
         seen = world
-        for _ in range(steps):
-            e, r, g, seen = batch_pass(jobs, SR, dur, dist, world, render_fn)
+        for i in range(steps):
+            e, r, g, seen = batch_pass(jobs, SR, dur, dist, world, render_fn, keep=keep if name == "literal" and i == steps - 1 else None)
             el += e; rs += r; gs += g
         samples = len(jobs) * n * steps
         out[name] = {"jobs": len(jobs), "seconds_per_job": dur, "samples_per_s": samples / el, "x_realtime": samples / el / SR,
@@ -375,6 +399,50 @@ def batch_bench(dist, world, steps, warmup, scaled_jobs_per_gpu=8192, scaled_dur
                      "scaling": "strong" if name == "literal" else "weak",
                      "valu_frac": FLOPS_BATCH_JOB * samples / el / world / 1e12 / PEAK_FP64_VALU_TFLOPS}
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20240
+DUMP_ENGINE_ROWS = 16384           # engines whose block is written (all of them in a smaller pool): 16 384 x 512 f32 = 32 MB
+DUMP_ENGINE_RUN = 1024             # ... in runs of this many consecutive engines: one contiguous read of the output block per run
+DUMP_BATCH_JOBS = 32               # batch jobs whose render is written (fewer when their rows would exceed DUMP_MAX_BYTES)
+
+
+def dump_sample(n, k):
+    """The fixed, seeded subset of k out of n rows that --dump-outputs writes, ascending (all rows when k >= n)."""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+
+def dump_engine_runs(n):
+    """The engines --dump-outputs writes, as (first, count) runs, ascending: all n engines when n <= DUMP_ENGINE_ROWS, else
+    DUMP_ENGINE_ROWS // DUMP_ENGINE_RUN runs of DUMP_ENGINE_RUN consecutive engines at fixed, seeded, distinct run positions (a run of
+    1 024 engines holds every one of the 88 instance velocities)."""
+    if n <= DUMP_ENGINE_ROWS:
+        return [(0, n)]
+    starts = dump_sample(n // DUMP_ENGINE_RUN, max(1, DUMP_ENGINE_ROWS // DUMP_ENGINE_RUN)) * DUMP_ENGINE_RUN
+    return [(int(s), DUMP_ENGINE_RUN) for s in starts]
+
+
+def dump_batch_shape(n_jobs, n):
+    """(jobs, samples per job) that --dump-outputs writes of a batch grid of n_jobs jobs of n samples: up to DUMP_BATCH_JOBS whole
+    jobs inside DUMP_MAX_BYTES (room kept for the index array); a job longer than the whole budget is cut to its first samples."""
+    room = DUMP_MAX_BYTES - 8 * DUMP_BATCH_JOBS
+    k = max(1, min(DUMP_BATCH_JOBS, n_jobs, room // (4 * max(n, 1))))
+    return k, min(n, room // (4 * k))
+
+
+def write_outputs(dirpath, arrays):
+    """arrays: name -> ndarray, each written as DIR/<name>.npy (float32 stays float32, everything else float64)."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(dirpath, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), v)
 
 
 # ---------------------------------------------------------------------------------------------------------------- main
@@ -405,6 +473,13 @@ def main(argv=None):
                          "independently created plugin instances do (the pool is staggered with the test hook after the warm-up); 1 = a fresh pool "
                          "as it is: every instance was built at the same sample, all share one phase and ONE oscillator is computed per pool (the "
                          "best case, reported as the `shared_tremolo_phase` extra of the default run); G = that many groups")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline figure: the line's self-check (`verified`), the extras (other deliveries, sizes "
+                         "and configurations, the batch path's scaled grid), the CPU baseline.  Without it a run sets up, warms up, times "
+                         "--steps steps and prints the line; --no-extras / --no-cpu-baseline narrow a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step rendered as DIR/<name>.npy (a fixed, seeded sample of the "
+                         "engines / jobs; rank 0's pool)")
     args = ap.parse_args(argv)
     if args.steps is None:
         args.steps = 100 if args.workload == "engines" else 3
@@ -413,6 +488,9 @@ def main(argv=None):
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus, argv)
+    # the melange preamp's noise streams start from a clock seed unless OW_NOISE_SEED is set: fixed here so that every run of the same
+    # arguments renders from the same inputs
+    os.environ.setdefault("OW_NOISE_SEED", "1")
 
     global SR, EPOCH, FLOPS_TREMOLO, FLOPS_PREAMP, FLOPS_POST
     if args.host_rate != SR:
@@ -467,9 +545,21 @@ def main(argv=None):
         if dryrun:
             def fake(jobs, n=int(0.01 * SR)):
                 return np.stack([np.full(n, j["note"] * 1000 + j["velocity"], dtype=np.float32) for j in jobs])
-        b = batch_bench(dist, world, args.steps, args.warmup, render_fn=fake, **({"scaled_jobs_per_gpu": 64, "scaled_dur": 0.01, "literal_dur": 0.01} if dryrun else {}))
+        keep = {} if args.dump_outputs else None
+        b = batch_bench(dist, world, args.steps, args.warmup, render_fn=fake, grids=("literal", "scaled") if args.full else ("literal",), keep=keep,
+                        **({"scaled_jobs_per_gpu": 64, "scaled_dur": 0.01, "literal_dur": 0.01} if dryrun else {}))
+        if rank == 0 and keep is not None:
+            # job j of the literal grid is row j // world of rank (j mod world)'s slab
+            slabs = keep.pop("slabs")
+            n_jobs = b["literal"]["jobs"]
+            k_, m_ = dump_batch_shape(n_jobs, int(slabs[0].shape[1]))
+            jobs_ = dump_sample(n_jobs, k_)
+            audio_ = np.stack([slabs[j % world][j // world][:m_].cpu().numpy() for j in jobs_])
+            del slabs
+            write_outputs(args.dump_outputs, {"batch_audio": audio_, "batch_jobs": jobs_})
         if rank == 0:
             lit = b["literal"]
+            scaled = b.get("scaled")
             line = {
                 "metric": "audio samples/s, batch-render path (ml/render_model_notes.py grid, preamp-bench render semantics)",
                 "value": lit["samples_per_s"], "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -480,8 +570,8 @@ def main(argv=None):
                 # what scales and what cannot: the literal grid is STRONG scaling of a latency-bound job -- 512 jobs leave 7/8 of one chip idle and
                 # a serial stream does not get shorter on more chips, so its N-GPU figure cannot exceed ~1 x the 1-GPU one; the scaled grid
                 # (the same jobs repeated until every GPU holds 8 192) is the weak-scaling figure of this path
-                "scaling_figure": {"grid": "scaled", "scaling": "weak", "samples_per_s": b["scaled"]["samples_per_s"], "jobs": b["scaled"]["jobs"],
-                                   "pass_ms": b["scaled"]["pass_ms"], "gather_ms": b["scaled"]["gather_ms"]},
+                "scaling_figure": ({"grid": "scaled", "scaling": "weak", "samples_per_s": scaled["samples_per_s"], "jobs": scaled["jobs"],
+                                    "pass_ms": scaled["pass_ms"], "gather_ms": scaled["gather_ms"]} if scaled else None),
                 "scaling_note": ("`value` is the LITERAL grid (512 jobs x 5 s): strong scaling of a latency-bound job, by construction <= ~1 x at any N; "
                                  "`scaling_figure` (the scaled grid, 8 192 jobs per GPU) is the number to compare across N"),
                 "batch": b,
@@ -532,6 +622,7 @@ def main(argv=None):
         def timed_steps(sc, k_steps, profile=False):
             """k_steps of the script between barriers; max over ranks"""
             barrier()
+            sc.t_capture = 0.0
             ta = time.perf_counter()
             trace = [] if os.environ.get("OW_BENCH_STEP_MS") else None      # (diagnostic: wall time of every step to stderr)
             for _ in range(k_steps):
@@ -544,11 +635,13 @@ def main(argv=None):
             if trace is not None:
                 ms_ = np.diff(np.array([ta] + trace)) * 1e3
                 print(f"[step ms] {k_steps} steps: " + " ".join(f"{x:.2f}" for x in ms_) + f" | closing barrier {1e3 * (time.perf_counter() - tb):.2f} ms", file=sys.stderr)
+            # the --dump-outputs read-out (rank 0 only) is taken back out of every rank's time: the other ranks waited for it in the barrier
+            cap_ = sc.t_capture
             if dist is not None:
-                t_ = torch.tensor([el_], dtype=torch.float64, device=red_dev)
+                t_ = torch.tensor([el_, cap_], dtype=torch.float64, device=red_dev)
                 dist.all_reduce(t_, op=dist.ReduceOp.MAX)
-                el_ = float(t_.item())
-            return el_
+                el_, cap_ = (float(x) for x in t_.tolist())
+            return el_ - cap_
 
         def side_run(p, n, k_warm, k_steps, epoch=None, buf=BUF, pos=None):
             """a short profiled run of another configuration (extras): value, ms per step and per kernel"""
@@ -585,23 +678,56 @@ def main(argv=None):
         script = Script(pool, n_inst, host_out=main_host)
         for _ in range(args.warmup):
             script.step()
+        dump_rows = dump_pieces = None
+        if args.dump_outputs and rank == 0:
+            runs = dump_engine_runs(n_inst)
+            dump_rows = np.concatenate([np.arange(s, s + c) for s, c in runs])
+            dump_pieces = []
+
+            def grab(length):
+                """the sampled engines of what the last render call delivered: from the pinned host block (--deliver host), else from
+                the output block in HBM, one contiguous read per run of engines (only the rows written, not the whole block)"""
+                import ctypes
+                if main_host is not None:
+                    blk = np.ctypeslib.as_array((ctypes.c_float * (n_inst * main_host[1])).from_address(main_host[0])).reshape(n_inst, main_host[1])
+                    return np.concatenate([blk[s:s + c, :length] for s, c in runs])
+                if dryrun:
+                    return np.array(pool.last_block()[dump_rows, :length])
+                ptr, ld = pool.device_output()
+                out = np.empty((dump_rows.size, ld), dtype=np.float32)
+                r = 0
+                for s, c in runs:
+                    dst = out[r:r + c]
+                    if ow.load_library().ow_test_device_read(dst.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ptr + 4 * s * ld), dst.nbytes, local_rank) != 0:
+                        raise RuntimeError("--dump-outputs: ow_test_device_read failed")
+                    r += c
+                return np.array(out[:, :length])
+
+            script.capture = lambda length: dump_pieces.append(grab(length))
+            script.capture_from = script.pos + (args.steps - 1) * BUF
         pool.set_profiling(True)
         elapsed = timed_steps(script, args.steps, profile=True)
         # melange power amp: Newton passes per chain-rate sample, mean over the engines, in the LAST block of the timed region
         pa_passes = float(pool.power_amp_passes().mean()) / (BUF * (2 if SR < 88200.0 else 1)) if pa_kind else None
         pool.set_profiling(False)
-        verified, verify_details = verify(pool, n_inst)
+        if dump_pieces is not None:
+            script.capture = None
+            dump_pieces.append(grab(BUF - sum(x.shape[1] for x in dump_pieces)))
+            write_outputs(args.dump_outputs, {"audio": np.concatenate(dump_pieces, axis=1), "audio_engines": dump_rows})
         on_traj = pool.trajectory_info()[0]
-        failed_ranks = [] if verified else [rank]
-        if dist is not None:
-            t_ = torch.zeros(world, dtype=torch.float64, device=red_dev)     # one slot per rank: which ranks failed, not just whether one did
-            t_[rank] = 0.0 if verified else 1.0
-            dist.all_reduce(t_, op=dist.ReduceOp.SUM)
-            failed_ranks = [r for r, x in enumerate(t_.tolist()) if x > 0.5]
-            verified = not failed_ranks
+        verified, verify_details, failed_ranks = None, None, []
+        if args.full:
+            verified, verify_details = verify(pool, n_inst)
+            failed_ranks = [] if verified else [rank]
+            if dist is not None:
+                t_ = torch.zeros(world, dtype=torch.float64, device=red_dev)     # one slot per rank: which ranks failed, not just whether one did
+                t_[rank] = 0.0 if verified else 1.0
+                dist.all_reduce(t_, op=dist.ReduceOp.SUM)
+                failed_ranks = [r for r, x in enumerate(t_.tolist()) if x > 0.5]
+                verified = not failed_ranks
 
         extras = {}
-        if not args.no_extras and not dryrun:
+        if args.full and not args.no_extras and not dryrun:
             # (a) PCIe-inclusive: the same steps with every block delivered into a pinned host buffer (what render(&mut [f32]) hands back,
             # engine.rs:425-462): big pools store the rows from the chain kernel itself (k_chain_stream), nothing is copied afterwards
             host = pool.alloc_host_block(BUF)
@@ -631,7 +757,7 @@ def main(argv=None):
             pool.free_host_block(main_host)
         pool.close()
 
-        if not args.no_extras and not dryrun and phases * 4 >= n_inst:
+        if args.full and not args.no_extras and not dryrun and phases * 4 >= n_inst:
             # (a2) the per-instance oscillators of rounds 1-3 on the same workload: a pool created without the shared trajectory
             # (OW_TREM_TRAJ=0), staggered to one oscillator per instance; then the same with the block-ahead oscillators serialised in front
             # of the voices (every kernel's HIP-event interval is then its own time)
@@ -651,7 +777,7 @@ def main(argv=None):
             extras["tremolo_per_instance_serialised"] = r
             pt.close()
 
-        if not args.no_extras and not dryrun and SR == 48000.0 and not preamp_kind and not pa_kind:
+        if args.full and not args.no_extras and not dryrun and SR == 48000.0 and not preamp_kind and not pa_kind:
             # (a3) the neighbouring BASELINE configs on the same pool size, short runs: configs[2] (96 kHz host, no oversampling) and the
             # melange 12-node preamp the north star names (literal per-sample rebuild)
             p3 = make_pool(n_inst, sr=96000.0, n_phases=phases)
@@ -681,7 +807,7 @@ def main(argv=None):
 
         single = None
         cpu = None
-        if rank == 0 and not args.no_extras and not dryrun:
+        if rank == 0 and args.full and not args.no_extras and not dryrun:
             lib = ow.load_library()
 
             def run256(cold):
@@ -794,10 +920,10 @@ def main(argv=None):
             one.close()
             extras["single_instance_cold_64"] = {"latency_us_mean": float(np.mean(lat) * 1e6), "x_realtime": 64 / float(np.mean(lat)) / SR,
                                                  "note": "64-sample buffers back to back on a fresh store: the instance waits for its own oscillator"}
-        if not args.no_extras and not dryrun:
+        if args.full and not args.no_extras and not dryrun:
             barrier()
             extras["batch"] = batch_bench(dist, world, steps=2, warmup=1)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline and not dryrun:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not dryrun:
             cpu = cpu_baseline(preamp_kind=preamp_kind)
 
         if rank == 0:

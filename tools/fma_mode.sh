@@ -5,9 +5,9 @@
 O=gpurun_out/fma; mkdir -p $O
 for v in default fma; do
   if [ $v = fma ]; then export OPENWURLI_HIP_LIB=$PWD/openwurli_amd/lib/libow_fma.so; else unset OPENWURLI_HIP_LIB; fi
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err
-  timeout 600 python bench.py --preamp melange --instances 65536 --steps 10 --warmup 3 --no-extras --no-cpu-baseline > $O/melange_$v.json 2> $O/melange_$v.err
-  timeout 900 python bench.py --power-amp melange --instances 65536 --steps 2 --warmup 3 --no-extras --no-cpu-baseline > $O/mpa_$v.json 2> $O/mpa_$v.err
+  timeout 600 python bench.py --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err
+  timeout 600 python bench.py --preamp melange --instances 65536 --steps 10 --warmup 3 --full --no-extras --no-cpu-baseline > $O/melange_$v.json 2> $O/melange_$v.err
+  timeout 900 python bench.py --power-amp melange --instances 65536 --steps 2 --warmup 3 --full --no-extras --no-cpu-baseline > $O/mpa_$v.json 2> $O/mpa_$v.err
   python - <<PY
 import json
 for n in ("bench", "melange", "mpa"):

@@ -65,7 +65,7 @@ pmc p256 mem "$G5" --instances 256 --steps 10 --warmup 2
 fi
 if [[ $PART == *C* ]]; then
 # ---- 4. bench lines behind every row of DESIGN section 6
-timeout 900 python bench.py > $O/bench_default.log 2>&1
+timeout 900 python bench.py --full > $O/bench_default.log 2>&1
 timeout 900 python bench.py --steps 20 --warmup 5 --no-extras > $O/bench_driver_like.log 2>&1
 timeout 900 python bench.py --steps 938 --warmup 5 --no-extras > $O/bench_10s.log 2>&1
 OW_TREM_TRAJ=0 timeout 900 python bench.py --steps 40 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_per_instance_oscillators.log 2>&1
@@ -75,13 +75,13 @@ timeout 900 python bench.py --host-rate 96000 --steps 40 --warmup 5 --no-extras 
 timeout 900 python bench.py --preamp melange --instances 65536 --steps 20 --warmup 3 --no-extras > $O/bench_melange.log 2>&1
 timeout 900 python bench.py --power-amp melange --steps 4 --warmup 3 --no-extras --no-cpu-baseline > $O/bench_power_amp_melange.log 2>&1
 timeout 900 python bench.py --power-amp melange --instances 16384 --steps 4 --warmup 3 --no-extras --no-cpu-baseline > $O/bench_power_amp_melange_16384.log 2>&1
-timeout 900 python bench.py --workload batch > $O/bench_batch.log 2>&1
+timeout 900 python bench.py --workload batch --full > $O/bench_batch.log 2>&1
 timeout 900 python bench.py --instances 256 --steps 100 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_p256.log 2>&1
 # round 5: config 2 as the API delivers it (every block into the caller's pinned host block, ten re-strikes inside), the 8-rank host
 # share priced on one GPU (two host threads: what LOCAL_WORLD_SIZE = 8 leaves a rank of a 16-CPU quota), a fresh 256-instance process
 timeout 900 python bench.py --steps 938 --warmup 5 --no-extras --no-cpu-baseline --deliver host > $O/bench_10s_host.log 2>&1
 OW_HOST_THREADS=2 timeout 900 python bench.py --steps 938 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_10s_2threads.log 2>&1
-OW_HOST_THREADS=2 timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_like_2threads.log 2>&1
+OW_HOST_THREADS=2 timeout 900 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench_driver_like_2threads.log 2>&1
 timeout 900 python bench.py --instances 256 --steps 30 --warmup 3 --no-extras --no-cpu-baseline > $O/bench_p256_fresh.log 2>&1
 timeout 900 python tools/probe_fused.py > $O/probe_fused.log 2>&1
 # the wave-level counters need the library built with -DOW_DBG_COUNTERS: rebuilt HERE from the round's sources (round 5 ran a stale one
