@@ -30,9 +30,9 @@ typedef struct ow_engine ow_engine;
 
 /* Version of this header's struct layouts and signatures.  ow_abi_version() returns the value the library was built with; a binding
  * checks it once after loading.  The by-pointer configuration structs (ow_batch_cfg, ow_midi_render_cfg) additionally carry their own
- * size in their first field, and ow_batch_cfg the size of one ow_job: a caller built against another header is refused ("ABI mismatch",
+ * size in their first field, and ow_batch_cfg / ow_calibrate_cfg the size of one ow_job / ow_calib_point: a caller built against another header is refused ("ABI mismatch",
  * negative return) instead of having fields read past the end of what it passed. */
-#define OW_ABI_VERSION 4
+#define OW_ABI_VERSION 5
 int ow_abi_version(void);
 
 /* VoiceState, crates/openwurli-dsp/src/engine.rs:30-37 */
@@ -327,6 +327,49 @@ typedef struct ow_midi_render_stats { uint64_t n_samples, note_ons, peak_polypho
  * Returns the longest job's sample count, <0 on error (e.g. stride too small, NaN times). */
 long long ow_render_midi(const ow_timed_event* events, const size_t* job_offsets, size_t n_jobs, const ow_midi_render_cfg* cfg,
                          double* out, size_t stride, ow_midi_render_stats* stats);
+
+/* ---- calibration sweep (`preamp-bench calibrate` / `sensitivity`, tools/preamp-bench/src/main.rs:1069-1395) ---------------- */
+/* One grid point: a (note, velocity byte) pair under its own CalibrationConfig (crates/openwurli-dsp/src/tables.rs:254-277), so a whole
+ * `sensitivity` sweep -- several configs -- is one call.  CalibrationConfig::default() is ds_at_c4 0.85, ds_exponent 0.75, ds_clamp
+ * (0.02, 0.95), target_db -35, voicing_slope -0.04, zero_trim 0; `calibrate` itself defaults to ds_at_c4 0.75 and ds_clamp_hi 0.82. */
+typedef struct ow_calib_point {
+    uint8_t note;          /* 33..96 (MIDI_LO..MIDI_HI, tables.rs:6-7: the tables are defined there; other notes are refused) */
+    uint8_t velocity;      /* 0..127, a MIDI velocity byte (velocity = byte / 127, main.rs:1147); larger values are refused */
+    uint8_t zero_trim;     /* CalibrationConfig.zero_trim */
+    uint8_t reserved[5];
+    double ds_at_c4, ds_exponent, ds_clamp_lo, ds_clamp_hi, target_db, voicing_slope;
+} ow_calib_point;
+typedef struct ow_calibrate_cfg {
+    uint32_t struct_size;  /* = sizeof(ow_calibrate_cfg) of the caller's header */
+    uint32_t point_size;   /* = sizeof(ow_calib_point) of the caller's header (the stride of `points`) */
+    double volume;         /* --volume (default 0.40; applied squared in front of the power amp) */
+    double speaker;        /* --speaker character (default 1.0) */
+    int device;
+    int preamp_kind;       /* --model dk of the default build / dk-legacy: OW_PREAMP_LEGACY8; dk of a melange-preamp build: OW_PREAMP_MELANGE12 */
+    int power_amp_kind;    /* the build's PowerAmp::new() (main.rs:1212): OW_POWER_AMP_BEHAVIORAL or OW_POWER_AMP_MELANGE (44.1 kHz, rail sag on) */
+    int reserved;
+} ow_calibrate_cfg;
+/* CalibrateRow (main.rs:1099-1121), same fields in the same order; dB values carry the reference's -120 floors. */
+typedef struct ow_calibrate_row {
+    uint8_t midi, velocity;
+    uint8_t reserved[6];
+    double ds_at_c4, ds_actual, y_peak;
+    double t2_peak_db, t2_rms_db, t2_h2_h1_db;
+    double t3_peak_db, t3_rms_db;
+    double t4_peak_db, t4_rms_db, t4_h2_h1_db;
+    double t5_peak_db, t5_rms_db, t5_h2_h1_db;
+    double proxy_db, trim_db, proxy_error_db, tanh_compression_db;
+} ow_calibrate_row;
+#define OW_CALIB_SAMPLES 22050   /* 0.5 s at BASE_SR 44 100 Hz (main.rs:27,1137) */
+/* run_calibrate (main.rs:1128-1262) for n points at once, lane = point, at 44.1 kHz: T1 ModalReed::new(.., onset 0, ..) without MLP or
+ * attack noise, T2 Pickup::new_with_scale(ds_actual), T3 x output_scale_with_config, T4 a fresh preamp (new + set_ldr_resistance(1e6)) with
+ * per-sample 2x oversampling, T5 x volume^2 -> PowerAmp::new() -> Speaker(character) -> x POST_SPEAKER_GAIN; metrics over samples
+ * [4410, 17640).  Large grids run in chunks of a fixed device-memory budget (OW_CALIB_CHUNK=<points> caps a chunk; tests use it).
+ * rows_out: [n].  taps_out: NULL or host f64 [n][5][taps_stride >= OW_CALIB_SAMPLES] receiving T1..T5.
+ * Returns 0, <0 on error (ow_last_error says why: "ABI mismatch", a note outside 33..96, a velocity above 127, an invalid clamp, a
+ * device error). */
+int ow_calibrate(const ow_calib_point* points, size_t n, const ow_calibrate_cfg* cfg, ow_calibrate_row* rows_out, double* taps_out,
+                 size_t taps_stride);
 
 #ifdef __cplusplus
 }

@@ -38,7 +38,7 @@ class OwMidiEvent(C.Structure):
 MIDI_DTYPE = [("engine", "<u4"), ("type", "u1"), ("note", "u1"), ("reserved", "<u2"), ("value", "<f4")]
 
 
-ABI_VERSION = 4      # include/openwurli_hip.h OW_ABI_VERSION; load_library() checks it against ow_abi_version()
+ABI_VERSION = 5      # include/openwurli_hip.h OW_ABI_VERSION; load_library() checks it against ow_abi_version()
 
 
 class OwBatchCfg(C.Structure):
@@ -74,6 +74,32 @@ class OwMidiRenderCfg(C.Structure):
 
 class OwMidiRenderStats(C.Structure):
     _fields_ = [("n_samples", C.c_uint64), ("note_ons", C.c_uint64), ("peak_polyphony", C.c_uint64)]
+
+
+class OwCalibPoint(C.Structure):
+    _fields_ = [("note", C.c_uint8), ("velocity", C.c_uint8), ("zero_trim", C.c_uint8), ("reserved", C.c_uint8 * 5),
+                ("ds_at_c4", C.c_double), ("ds_exponent", C.c_double), ("ds_clamp_lo", C.c_double), ("ds_clamp_hi", C.c_double),
+                ("target_db", C.c_double), ("voicing_slope", C.c_double)]
+
+
+class OwCalibrateCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("point_size", C.c_uint32), ("volume", C.c_double), ("speaker", C.c_double),
+                ("device", C.c_int), ("preamp_kind", C.c_int), ("power_amp_kind", C.c_int), ("reserved", C.c_int)]
+
+    def __init__(self, volume=0.40, speaker=1.0, device=0, preamp_kind=0, power_amp_kind=0):
+        super().__init__(C.sizeof(OwCalibrateCfg), C.sizeof(OwCalibPoint), volume, speaker, device, preamp_kind, power_amp_kind, 0)
+
+
+CALIBRATE_ROW_FIELDS = ("ds_at_c4", "ds_actual", "y_peak", "t2_peak_db", "t2_rms_db", "t2_h2_h1_db", "t3_peak_db", "t3_rms_db",
+                        "t4_peak_db", "t4_rms_db", "t4_h2_h1_db", "t5_peak_db", "t5_rms_db", "t5_h2_h1_db", "proxy_db", "trim_db",
+                        "proxy_error_db", "tanh_compression_db")
+
+
+class OwCalibrateRow(C.Structure):
+    _fields_ = [("midi", C.c_uint8), ("velocity", C.c_uint8), ("reserved", C.c_uint8 * 6)] + [(f, C.c_double) for f in CALIBRATE_ROW_FIELDS]
+
+
+CALIB_SAMPLES = 22050   # include/openwurli_hip.h OW_CALIB_SAMPLES
 
 
 # every symbol include/openwurli_hip.h declares: name -> (restype, argtypes)
@@ -155,6 +181,7 @@ SYMBOLS = {
     "ow_alias_audit_run": (C.c_int, [_VP, _VP, C.c_size_t, C.c_int, C.c_int, _VP, _VP, C.c_size_t]),
     "ow_smf_parse": (C.c_longlong, [_VP, C.c_size_t, C.c_int, _VP, C.c_size_t]),
     "ow_render_midi": (C.c_longlong, [_VP, _VP, C.c_size_t, _VP, _VP, C.c_size_t, _VP]),
+    "ow_calibrate": (C.c_int, [_VP, C.c_size_t, C.POINTER(OwCalibrateCfg), _VP, _VP, C.c_size_t]),
 }
 
 

@@ -180,6 +180,7 @@ struct Switches {
     bool pipe_overlap = false;
     bool host_profile = false;
     int midi_threads = 0;                      // OW_MIDI_THREADS
+    long long calib_chunk = 0;                 // OW_CALIB_CHUNK=n: at most n points per chunk of ow_calibrate (tests); 0: the device-memory budget alone
     static int flag(const char* name, int dflt) { const char* e = std::getenv(name); return (e && e[0]) ? (e[0] - '0') : dflt; }
     static Switches from_env() {
         Switches w;
@@ -209,6 +210,7 @@ struct Switches {
         w.out_direct = flag("OW_OUT_DIRECT", -1); if (w.out_direct > 1 || w.out_direct < -1) w.out_direct = -1;
         w.host_profile = std::getenv("OW_HOST_PROFILE") != nullptr;
         if (const char* e = std::getenv("OW_MIDI_THREADS")) { const long v = std::atol(e); if (v >= 1 && v <= 64) w.midi_threads = (int)v; }
+        if (const char* e = std::getenv("OW_CALIB_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.calib_chunk = v; }
         return w;
     }
 };

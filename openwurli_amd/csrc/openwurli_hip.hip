@@ -32,6 +32,7 @@
 #include "ow_trem_row.h"
 #include "ow_chain_row.h"
 #include "ow_audit.h"
+#include "ow_calib_kernels.h"
 #include "ow_midi_kernels.h"
 #include "ow_chain_wide.h"
 #include "ow_chain_stream.h"
@@ -57,3 +58,4 @@ using owdev::OwEngineOut;
 #include "host/api_offline.inc"         // C-ABI: render_note, batch render, WAV writers, feature stage
 #include "host/api_alias_audit.inc"     // C-ABI: the click-band alias audit (alias_audit.rs)
 #include "host/api_midi_render.inc"     // C-ABI: `preamp-bench render-midi` (SMF reader, voice manager, chain)
+#include "host/api_calibrate.inc"       // C-ABI: `preamp-bench calibrate` / `sensitivity` (the calibration sweep)

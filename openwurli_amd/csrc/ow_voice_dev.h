@@ -654,8 +654,10 @@ struct VoiceRegs {
     // dependent global load per mode per sample for as long as a released voice rings (measured: the played workload's bottleneck).
     // onset_tab / damp_tab: this sample's onset gain / the seven damper-ramp factors exp(-rate t / ramp), evaluated ahead for the
     // whole chunk by k_voice (lane-parallel over the samples), or nullptr to evaluate them here.
+    // reed_tap: nullptr, or where the reed sum of this sample goes (ModalReed::render's output before attack noise and pickup; the
+    // calibration sweep's T1 tap).  Every voice kernel passes nullptr, which the inlined step compiles away.
     OW_DEV double step(const double* __restrict__ lcoef, const double* __restrict__ onset_tab = nullptr,
-                       const double* __restrict__ damp_tab = nullptr) {
+                       const double* __restrict__ damp_tab = nullptr, double* __restrict__ reed_tap = nullptr) {
 #ifndef OW_STRICT_FP
 #pragma clang fp contract(fast)
 #endif
@@ -728,6 +730,7 @@ struct VoiceRegs {
         }
         sample += 1ull;
         double x = 0.0 + sum;
+        if (reed_tap) *reed_tap = x;
         if (!STEADY && noise_rem > 0u) {
             double e = 1.0;
             if (noise_fade > 0u) {
