@@ -30,9 +30,10 @@ typedef struct ow_engine ow_engine;
 
 /* Version of this header's struct layouts and signatures.  ow_abi_version() returns the value the library was built with; a binding
  * checks it once after loading.  The by-pointer configuration structs (ow_batch_cfg, ow_midi_render_cfg) additionally carry their own
- * size in their first field, and ow_batch_cfg / ow_calibrate_cfg the size of one ow_job / ow_calib_point: a caller built against another header is refused ("ABI mismatch",
+ * size in their first field, and ow_batch_cfg / ow_calibrate_cfg / ow_preamp_measure_cfg the size of one ow_job / ow_calib_point / ow_preamp_point: a caller built
+ * against another header is refused ("ABI mismatch",
  * negative return) instead of having fields read past the end of what it passed. */
-#define OW_ABI_VERSION 5
+#define OW_ABI_VERSION 6
 int ow_abi_version(void);
 
 /* VoiceState, crates/openwurli-dsp/src/engine.rs:30-37 */
@@ -370,6 +371,40 @@ typedef struct ow_calibrate_row {
  * device error). */
 int ow_calibrate(const ow_calib_point* points, size_t n, const ow_calibrate_cfg* cfg, ow_calibrate_row* rows_out, double* taps_out,
                  size_t taps_stride);
+
+/* ---- preamp measurements (`preamp-bench gain` / `sweep` / `harmonics` / `tremolo-sweep`, tools/preamp-bench/src/main.rs:150-369) ---- */
+/* One measurement point: a sine of freq_hz / amplitude through a fresh Oversampler and the 2x-oversampled preamp, 22 050 samples at BASE_SR
+ * (measure_gain_at :157-190, cmd_harmonics :256-323).  r_ldr is what set_ldr_resistance receives (:620-626: clamp to 1 kohm, 0.01 ohm
+ * hysteresis).  r_reset is the LDR resistance the legacy preamp's DC solve runs at before that: reset() solves DC at the PREVIOUS
+ * self.r_ldr (dk_preamp_legacy.rs:628-640), so point i of a `sweep` / `tremolo-sweep` -- one preamp object, reset per point (:217-254,
+ * :325-368) -- starts from the DC state of point i-1's resistance; `gain`, `harmonics` and point 0 start from new(), i.e. 1e6.  The
+ * melange preamp's reset() clones its settled state and ignores r_reset.  With r_reset explicit every point is independent. */
+typedef struct ow_preamp_point { double freq_hz, amplitude, r_ldr, r_reset; } ow_preamp_point;
+typedef struct ow_preamp_measure_cfg {
+    uint32_t struct_size;  /* = sizeof(ow_preamp_measure_cfg) of the caller's header */
+    uint32_t point_size;   /* = sizeof(ow_preamp_point) of the caller's header (the stride of `points`) */
+    int device;
+    int preamp_kind;       /* create_preamp (:132-148): `--model dk` of the default build / dk-legacy: OW_PREAMP_LEGACY8; dk of a melange-preamp build: OW_PREAMP_MELANGE12 */
+    int reserved[4];
+} ow_preamp_measure_cfg;
+/* gain = peak |out| over [OW_PBENCH_GAIN_LO, OW_PBENCH_SAMPLES) / amplitude (measure_gain_at), gain_db = 20 log10(gain); h[k-1] =
+ * dft_magnitude (:893-903) at k x freq_hz over [OW_PBENCH_HARM_LO, OW_PBENCH_SAMPLES), k = 1..5; thd_pct and h2_h3_db as cmd_harmonics forms
+ * them (h2_h3_db = INFINITY when h3 <= 1e-15).  Both windows come from the same single run. */
+typedef struct ow_preamp_measure_row {
+    double freq_hz, amplitude, r_ldr;
+    double gain, gain_db;
+    double h[5];
+    double thd_pct, h2_h3_db;
+} ow_preamp_measure_row;
+#define OW_PBENCH_SAMPLES 22050  /* (BASE_SR * 0.5) as usize (:266); = (BASE_SR * 0.3) + (BASE_SR * 0.2) settle + measure (:165-166) */
+#define OW_PBENCH_GAIN_LO 13230  /* (BASE_SR * 0.3) as usize: the settle of measure_gain_at */
+#define OW_PBENCH_HARM_LO 16537  /* output.len() * 3 / 4: cmd_harmonics' last quarter */
+/* n points at once.  rows_out: [n].  trace_out: NULL or host f64 [n][trace_stride >= OW_PBENCH_SAMPLES] receiving the base-rate preamp
+ * output (downsample_2x's); with a trace the grid runs in chunks of a fixed device-memory budget (OW_PBENCH_CHUNK=<points> caps them).
+ * Returns 0, <0 on error (ow_last_error says why: "ABI mismatch", a non-finite or non-positive freq_hz / amplitude / r_ldr / r_reset,
+ * a short trace_stride, a device error). */
+int ow_preamp_measure(const ow_preamp_point* points, size_t n, const ow_preamp_measure_cfg* cfg, ow_preamp_measure_row* rows_out,
+                      double* trace_out, size_t trace_stride);
 
 #ifdef __cplusplus
 }

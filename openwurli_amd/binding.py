@@ -38,7 +38,7 @@ class OwMidiEvent(C.Structure):
 MIDI_DTYPE = [("engine", "<u4"), ("type", "u1"), ("note", "u1"), ("reserved", "<u2"), ("value", "<f4")]
 
 
-ABI_VERSION = 5      # include/openwurli_hip.h OW_ABI_VERSION; load_library() checks it against ow_abi_version()
+ABI_VERSION = 6      # include/openwurli_hip.h OW_ABI_VERSION; load_library() checks it against ow_abi_version()
 
 
 class OwBatchCfg(C.Structure):
@@ -100,6 +100,28 @@ class OwCalibrateRow(C.Structure):
 
 
 CALIB_SAMPLES = 22050   # include/openwurli_hip.h OW_CALIB_SAMPLES
+
+
+class OwPreampPoint(C.Structure):
+    _fields_ = [("freq_hz", C.c_double), ("amplitude", C.c_double), ("r_ldr", C.c_double), ("r_reset", C.c_double)]
+
+
+class OwPreampMeasureCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("point_size", C.c_uint32), ("device", C.c_int), ("preamp_kind", C.c_int),
+                ("reserved", C.c_int * 4)]
+
+    def __init__(self, device=0, preamp_kind=0):
+        super().__init__(C.sizeof(OwPreampMeasureCfg), C.sizeof(OwPreampPoint), device, preamp_kind)
+
+
+class OwPreampMeasureRow(C.Structure):
+    _fields_ = [("freq_hz", C.c_double), ("amplitude", C.c_double), ("r_ldr", C.c_double), ("gain", C.c_double), ("gain_db", C.c_double),
+                ("h", C.c_double * 5), ("thd_pct", C.c_double), ("h2_h3_db", C.c_double)]
+
+
+PBENCH_SAMPLES = 22050   # include/openwurli_hip.h OW_PBENCH_SAMPLES
+PBENCH_GAIN_LO = 13230   # OW_PBENCH_GAIN_LO
+PBENCH_HARM_LO = 16537   # OW_PBENCH_HARM_LO
 
 
 # every symbol include/openwurli_hip.h declares: name -> (restype, argtypes)
@@ -182,6 +204,7 @@ SYMBOLS = {
     "ow_smf_parse": (C.c_longlong, [_VP, C.c_size_t, C.c_int, _VP, C.c_size_t]),
     "ow_render_midi": (C.c_longlong, [_VP, _VP, C.c_size_t, _VP, _VP, C.c_size_t, _VP]),
     "ow_calibrate": (C.c_int, [_VP, C.c_size_t, C.POINTER(OwCalibrateCfg), _VP, _VP, C.c_size_t]),
+    "ow_preamp_measure": (C.c_int, [_VP, C.c_size_t, C.POINTER(OwPreampMeasureCfg), _VP, _VP, C.c_size_t]),
 }
 
 
