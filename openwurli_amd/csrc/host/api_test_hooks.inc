@@ -335,6 +335,7 @@ int ow_test_pool_set_switch(ow_pool* p, const char* name, int value) {
     else if (n == "chain_stream") w.chain_stream = value < 0 ? -1 : (value != 0);
     else if (n == "chain_row") w.chain_row = value < 0 ? -1 : (value != 0);
     else if (n == "post_pair") w.post_pair = value < 0 ? -1 : (value != 0);
+    else if (n == "preamp_pair") w.preamp_pair = value < 0 ? -1 : (value != 0);
     else return -1;                                       // (trem_traj / trem_cache / pipe shape the pool at creation: environment only)
     return 0;
 }
@@ -370,6 +371,7 @@ int ow_test_pool_get_switch(const ow_pool* p, const char* name) {
     if (n == "midi_device_bursts") return (int)std::min<uint64_t>(p->vm_bursts, 0x7FFFFFFF);
     if (n == "chain_stream") return w.chain_stream;
     if (n == "post_pair") return w.post_pair;
+    if (n == "preamp_pair") return w.preamp_pair;
     return -2;
 }
 // Engines of the pool that read the shared trajectory / samples the store of the pool's rate holds (produced or enqueued) / its capacity.

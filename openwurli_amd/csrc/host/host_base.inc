@@ -176,6 +176,7 @@ struct Switches {
     int chain_row = -1;                        // OW_CHAIN_ROW=0/1: the fused chain launch with one solver state per row of sixteen lanes (k_chain_row) never / whenever the chain is fused; -1: ranges of <= 1 024 engines
     int chain_stream = -1;                     // OW_CHAIN_STREAM=0/1: preamp + output stage of a big oversampled pool as one launch (k_chain_stream); -1: when the block goes to a pinned host block
     int post_pair = -1;                        // OW_POST_PAIR=0/1: the oversampled output stage with lane = engine (k_post<false, true>) never / always; -1: ranges of >= 131 072 engines (two wavefronts per SIMD without the lane pair)
+    int preamp_pair = -1;                      // OW_PREAMP_PAIR=0/1: the legacy preamp on the lane path with lane = engine, main and shadow state in one lane (k_preamp_pair) never / always; -1: ranges of >= 131 072 engines
     int out_direct = -1;                       // OW_OUT_DIRECT=0/1: output stage stores straight into a pinned host block (ow_host_alloc) instead of d_out + copy; -1: default
     bool pipe_overlap = false;
     bool host_profile = false;
@@ -209,6 +210,7 @@ struct Switches {
         w.chain_row = flag("OW_CHAIN_ROW", -1); if (w.chain_row > 1 || w.chain_row < -1) w.chain_row = -1;
         w.chain_stream = flag("OW_CHAIN_STREAM", -1); if (w.chain_stream > 1 || w.chain_stream < -1) w.chain_stream = -1;
         w.post_pair = flag("OW_POST_PAIR", -1); if (w.post_pair > 1 || w.post_pair < -1) w.post_pair = -1;
+        w.preamp_pair = flag("OW_PREAMP_PAIR", -1); if (w.preamp_pair > 1 || w.preamp_pair < -1) w.preamp_pair = -1;
         w.out_direct = flag("OW_OUT_DIRECT", -1); if (w.out_direct > 1 || w.out_direct < -1) w.out_direct = -1;
         w.host_profile = std::getenv("OW_HOST_PROFILE") != nullptr;
         if (const char* e = std::getenv("OW_MIDI_THREADS")) { const long v = std::atol(e); if (v >= 1 && v <= 64) w.midi_threads = (int)v; }

@@ -680,6 +680,8 @@ void render_range(ow_pool* p, int e0, int ne, size_t len, bool with_voices, floa
                                                                              p->d_pre, p->d_noise, I, L, Lcap, se0, sne);
             else if (preamp_wide(p, sne))
                 owdev::k_preamp_wide<<<dim3((sne + 7) / 8), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, se0, sne);
+            else if (p->sw.preamp_pair < 0 ? sne >= 131072 : p->sw.preamp_pair == 1)     // lane = engine: half the wavefronts, two per SIMD from 131 072 engines
+                owdev::k_preamp_pair<<<dim3((sne + 63) / 64), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, se0, sne);
             else
                 owdev::k_preamp<<<dim3((sne + 31) / 32), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, se0, sne);
         }

@@ -4,6 +4,7 @@
 //   k_voice(_steady) lane = sounding voice (packed across engines by the host), ordered per-engine LDS reduction
 //   k_tremolo     lane = engine                    Twin-T oscillator + LDR -> R[n]
 //   k_preamp      lane = (engine, main|shadow)     half-band up + DK preamp (main - shadow)
+//   k_preamp_pair lane = engine (main and shadow)  the same for ranges of >= 131 072 engines
 //   k_post        lane = engine                    power amp x2 -> half-band down -> speaker -> gain -> f32
 //
 // All global traffic is coalesced: voice records are field-major [field][64 slots], chain state and the
@@ -1307,6 +1308,132 @@ __global__ __launch_bounds__(64) void k_preamp(const OwConsts* __restrict__ K, d
                 const uint64_t d = dbits(CSF(CS_DIAG));
                 CSF(CS_DIAG) = bitsd((d & 0xFFFFFFFFull) | ((uint64_t)((uint32_t)(d >> 32) + nan_resets) << 32));
             }
+        }
+    }
+}
+
+// PAIR: k_preamp with lane = engine, 64 engines per wavefront -- the lane holds the engine's main AND shadow state (dk_step_pair), so
+// the per-engine work (voice-sum staging, R reads, depth smoother and divider, g_ldr, both half-band up-samplers, sm_k / k00..k11, the
+// wave-uniform constant fetches) is paid once per engine instead of once per state, and main - shadow needs no lane exchange.  Half
+// the wavefronts of k_preamp: for ranges big enough to fill the chip at two per SIMD (the host's choice, `preamp_pair`).  Voice sums
+// staged in 32-sample chunks (64 rows x 33: no more LDS than k_preamp's tile).  Same operations per value: the same bits in `pre`, in
+// the state rows and in the output.
+#define OW_PPCHUNK 32
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_preamp_pair(const OwConsts* __restrict__ K, double* __restrict__ cs, const OwEngineArgs* __restrict__ args,
+                   const OwEngineOut* __restrict__ eout, const double* __restrict__ sum, const OwTremSrc tsrc,
+                   double* __restrict__ pre, int I, int L, int Lcap, int e0, int ne) {
+    __shared__ double tile[64 * (OW_PPCHUNK + 1)];
+    const int lane = threadIdx.x;
+    const int eb = e0 + blockIdx.x * 64;
+    const int e = eb + lane;
+    const bool valid = e < e0 + ne;
+    const int ec = valid ? e : (e0 + ne - 1);   // clamp so every lane runs the same (harmless) work
+    const int osr = K->oversample ? 2 : 1;
+
+    DkSt sm, ss;      // main (the audio), shadow (0.0: cancels the tremolo pump, dk_preamp_legacy.rs:585-608)
+    double ua[3], ub[3];
+    double r_ldr, g_ldr, g_prev;
+    Smoother sd;
+    {
+        const int e = ec;
+        smoother_load(sd, cs, I, e, CS_SM_DEPTH);
+        if (args[e].set_flags & 1u) sd.retarget(args[e].depth_target, K->ramp_samples);
+        dk_load(sm, cs, I, e, CS_P_MAIN);
+        dk_load(ss, cs, I, e, CS_P_SHADOW);
+        for (int i = 0; i < 3; ++i) { ua[i] = CSF(CS_OS_UA + i); ub[i] = CSF(CS_OS_UB + i); }
+        r_ldr = CSF(CS_P_RLDR); g_ldr = CSF(CS_P_GLDR); g_prev = CSF(CS_P_GPREV);
+        const uint64_t fl = dbits(CSF(CS_FLAGS));
+        if (fl & 1ull) {  // deferred preamp.reset() + oversampler.reset() from the output NaN guard (engine.rs:450-457)
+            dk_dc_reset(K, r_ldr, sm);
+            ss = sm;          // the DC solve is a function of r_ldr alone: both states get the same bits
+            g_ldr = 1.0 / r_ldr; g_prev = g_ldr;
+            for (int i = 0; i < 3; ++i) { ua[i] = 0.0; ub[i] = 0.0; }
+        }
+    }
+    uint32_t nan_resets = 0;
+    double sh_depth = __longlong_as_double(0x7FF8000000000000LL), sh_top = 0.0, sh_lower = 0.0;      // as k_preamp
+    // staging flags of engine row `lane` (see k_preamp); broadcast per row with v_readlane: lanes 0-31 stage row r, lanes 32-63 row r + 32
+    int rowflag = 0;
+    if (valid && !eout[e].sum_nonfinite) rowflag = (args[e].main_mask ? 1 : 0) | (args[e].steal_mask ? 2 : 0);
+    const int e_last = e0 + ne - 1;
+    const int half = lane >> 5;
+    const TremCol tcol = trem_col(tsrc, I, ec);
+    double rn[2];
+    rn[0] = trem_col_at(tcol, 0u);
+    rn[1] = osr == 2 ? trem_col_at(tcol, 1u) : 0.0;
+    for (int base = 0; base < L; base += OW_PPCHUNK) {
+        const int cn = min(OW_PPCHUNK, L - base);
+        const int col = base + min(lane & 31, cn - 1);
+#pragma unroll 8
+        for (int r = 0; r < 32; ++r) {
+            const int row = r + 32 * half;
+            const int er = min(eb + row, e_last);
+            const int fl_lo = __builtin_amdgcn_readlane(rowflag, r), fl_hi = __builtin_amdgcn_readlane(rowflag, r + 32);
+            const int fl = half ? fl_hi : fl_lo;
+            const double a = sum[((size_t)0 * I + er) * Lcap + col];
+            const double b = sum[((size_t)1 * I + er) * Lcap + col];
+            double x = (fl & 1) ? a : 0.0;
+            x = (fl & 2) ? x + b : x;
+            tile[row * (OW_PPCHUNK + 1) + (lane & 31)] = x;
+        }
+        __syncthreads();
+        for (int n = 0; n < cn; ++n) {
+            const double x = tile[lane * (OW_PPCHUNK + 1) + n];
+            const double rc[2] = {rn[0], rn[1]};
+            {
+                const uint32_t nx = (uint32_t)(min(base + n + 1, L - 1) * osr);
+                rn[0] = trem_col_at(tcol, nx);
+                if (osr == 2) rn[1] = trem_col_at(tcol, nx + 1u);
+            }
+            const double depth = clampd(sd.next(), 0.0, 1.0);   // engine.rs:533-534, tremolo.rs:117-119
+            if (__builtin_amdgcn_ballot_w64(!(depth == sh_depth)) != 0ull) {     // trem_shunt's depth-only part, as k_preamp
+                sh_depth = depth;
+                const double r_upper = 50000.0 * (1.0 - depth);
+                sh_lower = 50000.0 * depth;
+                sh_top = r_upper > 0.0 ? ow_div(r_upper * 18000.0, r_upper + 18000.0) : 0.0;
+            }
+            double in[2];
+            if (osr == 2) {  // Oversampler::upsample_2x (oversampler.rs:108-121)
+                in[0] = allpass3(OW_OS_A0, OW_OS_A1, OW_OS_A2, ua, x);
+                in[1] = allpass3(OW_OS_B0, OW_OS_B1, OW_OS_B2, ub, x);
+            } else {
+                in[0] = x;
+                in[1] = 0.0;
+            }
+            for (int j = 0; j < osr; ++j) {
+                const size_t idx = (size_t)((base + n) * osr + j);
+                const double branch = 680.0 + rc[j];
+                const double low = sh_lower > 0.0 ? ow_div(sh_lower * branch, sh_lower + branch) : 0.0;
+                const double r_new = fmax(sh_top + low, 1000.0);               // tremolo.rs:152-167; set_ldr_resistance, :620-626
+                if (fabs(r_new - r_ldr) > 0.01) { r_ldr = r_new; g_ldr = ow_div(1.0, r_new); }
+                double om, os;
+                dk_step_pair(sm, ss, in[j], 0.0, g_ldr, g_prev, K, om, os);     // shadow input 0.0 (dk_preamp_legacy.rs:599)
+                g_prev = g_ldr;                                                   // :604
+                double result = om - os;                                          // main - pump, :608
+                if (!isfinite(result)) {                                          // :610-615
+                    dk_dc_reset(K, r_ldr, sm);
+                    ss = sm;
+                    g_ldr = 1.0 / r_ldr; g_prev = g_ldr;
+                    result = 0.0;
+                    nan_resets += 1u;
+                }
+                if (valid) pre[idx * I + e] = result;
+            }
+        }
+        __syncthreads();
+    }
+    if (valid) {
+        dk_store(sm, cs, I, e, CS_P_MAIN);
+        dk_store(ss, cs, I, e, CS_P_SHADOW);
+        for (int i = 0; i < 3; ++i) { CSF(CS_OS_UA + i) = ua[i]; CSF(CS_OS_UB + i) = ub[i]; }
+        CSF(CS_P_RLDR) = r_ldr; CSF(CS_P_GLDR) = g_ldr; CSF(CS_P_GPREV) = g_prev;
+        smoother_store(sd, cs, I, e, CS_SM_DEPTH);
+        const uint64_t fl = dbits(CSF(CS_FLAGS));
+        if (fl & 1ull) CSF(CS_FLAGS) = bitsd(fl & ~1ull);
+        if (nan_resets) {
+            const uint64_t d = dbits(CSF(CS_DIAG));
+            CSF(CS_DIAG) = bitsd((d & 0xFFFFFFFFull) | ((uint64_t)((uint32_t)(d >> 32) + nan_resets) << 32));
         }
     }
 }
