@@ -50,6 +50,16 @@ int ow_debug_div_forms(int mode, const double* a, const double* b, const double*
  * tanh (expm1-based, <= 2 ulp) and tanh(); 2 / 3 / 4 the reed's onset gain (reed.rs:251-264: (0.5 (1 - cos x))^p as exp(p ln .)) at phase x
  * with p = 1.25 / 1.5 / 1.9 and the same expression with the library's pow(). */
 int ow_debug_unary(int which, const double* x, size_t n, double* fast, double* lib, int device);
+/* ONE step of the legacy DK preamp (DkPreamp::dk_step, dk_preamp_legacy.rs:447-554) on n independent cases at chain rate `rate`, through
+ * one of the kernels' four forms of it: form 0 = dk_step, one state per lane (k_preamp); 1 = dk_step_pair, one lane holds case 2k as its
+ * main and case 2k + 1 as its shadow state and uses case 2k's g_ldr / g_ldr_prev for both (k_preamp_pair); 2 = dk_step_wide, four lanes
+ * per state (k_preamp_wide, k_chain_fused); 3 = dk_step_row, sixteen lanes per state (k_chain_row).  The production device functions with
+ * the production constants of that rate; the state is prepared as at a block start (the fourteen fields, then the junctions'
+ * transconductances at v_nl).  states_in / states_out: [n][14] = j_cin, cin_rhs_prev, v[8], i_nl[2], v_nl[2]; input, g_ldr, g_ldr_prev,
+ * out: [n] (out = the step's return value, v[OUT]).  Cases fill the wavefronts in order (64 / 128 / 16 / 4 cases per wavefront); n need
+ * not fill the last one.  Returns 0, <0 on error. */
+int ow_debug_dk_step(int form, double rate, const double* states_in, const double* input, const double* g_ldr, const double* g_ldr_prev, size_t n,
+                     double* states_out, double* out, int device);
 
 /* ---- tremolo phase groups -------------------------------------------------------------------- */
 /* Engines whose tremolo oscillators are bit-identical share one oscillator (a fresh pool is one group).  This hook cuts the pool into

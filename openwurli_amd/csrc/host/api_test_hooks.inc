@@ -490,4 +490,46 @@ int ow_debug_unary(int which, const double* x, size_t n, double* fast, double* l
         return 0;
     } catch (const std::exception& ex) { set_err(std::string("ow_debug_unary: ") + ex.what()); return -1; }
 }
+
+int ow_debug_dk_step(int form, double rate, const double* states_in, const double* input, const double* g_ldr, const double* g_ldr_prev, size_t n,
+                     double* states_out, double* out, int device) {
+    try {
+        if (!states_in || !input || !g_ldr || !g_ldr_prev || !states_out || !out || form < 0 || form > 3 || !(rate > 0.0)) throw std::runtime_error("bad argument");
+        if (n == 0) return 0;
+        if (n > (size_t)1 << 24) throw std::runtime_error("too many cases");
+        HIP_OK(hipSetDevice(device));
+        std::unique_ptr<OwConsts> hc(new OwConsts());
+        // build_consts takes the HOST rate; a host rate >= 88.2 kHz runs the chain at that rate without oversampling (engine.rs:195)
+        owhip::build_consts(*hc, rate < 88200.0 ? rate * 0.5 : rate, OW_PREAMP_LEGACY8);
+        if (hc->os_sr != rate) throw std::runtime_error("rate is not reachable as a chain rate");
+        std::vector<double> rows(14 * n);                      // the chain kernels' state rows: [field][case]
+        for (size_t c = 0; c < n; ++c)
+            for (int f = 0; f < 14; ++f) rows[(size_t)f * n + c] = states_in[c * 14 + f];
+        DevMem dK, dIn, dX, dG, dGp, dOut, dO;
+        dK.alloc(sizeof(OwConsts)); dIn.alloc(sizeof(double) * 14 * n); dOut.alloc(sizeof(double) * 14 * n);
+        dX.alloc(sizeof(double) * n); dG.alloc(sizeof(double) * n); dGp.alloc(sizeof(double) * n); dO.alloc(sizeof(double) * n);
+        HIP_OK(hipMemcpy(dK.p, hc.get(), sizeof(OwConsts), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dIn.p, rows.data(), sizeof(double) * 14 * n, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dX.p, input, sizeof(double) * n, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dG.p, g_ldr, sizeof(double) * n, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dGp.p, g_ldr_prev, sizeof(double) * n, hipMemcpyHostToDevice));
+        HIP_OK(hipMemset(dOut.p, 0, sizeof(double) * 14 * n));
+        HIP_OK(hipMemset(dO.p, 0, sizeof(double) * n));
+        const size_t per_wave[4] = {64, 128, 16, 4};            // cases of one wavefront: lane | lane = (main, shadow) | quad | row of sixteen
+        const dim3 grid((unsigned)((n + per_wave[form] - 1) / per_wave[form])), block(64);
+        const OwConsts* K = dK.as<OwConsts>();
+        switch (form) {
+            case 0: owdev::k_debug_dk_step<owdev::DKF_LANE><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
+            case 1: owdev::k_debug_dk_step<owdev::DKF_PAIR><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
+            case 2: owdev::k_debug_dk_step<owdev::DKF_WIDE><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
+            default: owdev::k_debug_dk_step<owdev::DKF_ROW><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
+        }
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpy(rows.data(), dOut.p, sizeof(double) * 14 * n, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(out, dO.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+        for (size_t c = 0; c < n; ++c)
+            for (int f = 0; f < 14; ++f) states_out[c * 14 + f] = rows[(size_t)f * n + c];
+        return 0;
+    } catch (const std::exception& ex) { set_err(std::string("ow_debug_dk_step: ") + ex.what()); return -1; }
+}
 }  // extern "C"

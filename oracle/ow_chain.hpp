@@ -123,6 +123,14 @@ inline void compute_k(const Mat8 s, double k[2][2]) {  // :414-425
 struct DkState {  // dk_preamp_legacy.rs:231-251
     double j_cin, cin_rhs_prev, v[8], i_nl[2], v_nl[2];
 };
+// Test instrumentation of DkPreamp::dk_step (owo_dk_step_cases): how one step's Newton loop went.  Observes, changes nothing.
+struct DkStepTrace {
+    enum { CONVERGED = 0, SINGULAR = 1, SIX_UPDATES = 2 };
+    int updates = 0;              // Newton updates taken (0..6)
+    int exit_kind = SIX_UPDATES;  // which way the loop was left
+    int clamp_lo = 0, clamp_hi = 0;  // junction evaluations of the step (loop and closing bjt_ic) whose argument lay below -1 V / above VBE_MAX
+    void see(double vbe) { clamp_lo += vbe < -1.0; clamp_hi += vbe > dk::VBE_MAX; }
+};
 
 struct DkPreamp {
     dk::Mat8 s_base, a_neg_base, g_dc_base;
@@ -241,7 +249,7 @@ struct DkPreamp {
     }
 
     // :447-554
-    double dk_step(DkState& st, double input) const {
+    double dk_step(DkState& st, double input, DkStepTrace* tr = nullptr) const {
         using namespace dk;
         Vec8 rhs;
         mat_vec_mul(a_neg_base, st.v, rhs);
@@ -267,18 +275,21 @@ struct DkPreamp {
         double v_nl[2] = {st.v_nl[0], st.v_nl[1]};
         for (int iter = 0; iter < 6; ++iter) {
             double ic0, gm0, ic1, gm1;
+            if (tr) { tr->see(v_nl[0]); tr->see(v_nl[1]); }
             bjt_ic_gm(v_nl[0], ic0, gm0);
             bjt_ic_gm(v_nl[1], ic1, gm1);
             const double f0 = v_nl[0] - p[0] - k00 * ic0 - k01 * ic1;
             const double f1 = v_nl[1] - p[1] - k10 * ic0 - k11 * ic1;
-            if (std::fabs(f0) < 1e-9 && std::fabs(f1) < 1e-9) break;
+            if (std::fabs(f0) < 1e-9 && std::fabs(f1) < 1e-9) { if (tr) tr->exit_kind = DkStepTrace::CONVERGED; break; }
             const double j00 = 1.0 - k00 * gm0, j01 = -k01 * gm1, j10 = -k10 * gm0, j11 = 1.0 - k11 * gm1;
             const double det = j00 * j11 - j01 * j10;
-            if (std::fabs(det) < 1e-30) break;
+            if (std::fabs(det) < 1e-30) { if (tr) tr->exit_kind = DkStepTrace::SINGULAR; break; }
             const double inv_det = 1.0 / det;
             v_nl[0] -= inv_det * (j11 * f0 - j01 * f1);
             v_nl[1] -= inv_det * (j00 * f1 - j10 * f0);
+            if (tr) tr->updates += 1;
         }
+        if (tr) { tr->see(v_nl[0]); tr->see(v_nl[1]); }
         const double ic_new[2] = {bjt_ic(v_nl[0]), bjt_ic(v_nl[1])};
         const double sfb_ni_dot_ic = sfb_ni[0] * ic_new[0] + sfb_ni[1] * ic_new[1];
         for (int i = 0; i < N; ++i) {

@@ -351,6 +351,36 @@ void owo_preamp_run(double sr, const double* x, const double* r, double r_static
     }
 }
 
+// DkPreamp::dk_step as a pure function of n independent cases at chain rate `sr` (tests/dk_step_cases.py): states [n][14] in the
+// owo_engine_preamp_state order (j_cin, cin_rhs_prev, v[8], i_nl[2], v_nl[2]), input / g_ldr / g_ldr_prev [n].  Each case takes ONE step of
+// the preamp's own dk_step.  states_out [n][14], out [n] = the step's return value, info [n][4] = Newton updates taken, how the loop was
+// left (0 converged, 1 |det| < 1e-30, 2 six updates), junction evaluations of the step clamped at -1 V, ... at VBE_MAX (DkStepTrace).
+void owo_dk_step_cases(double sr, const double* states, const double* input, const double* g_ldr, const double* g_ldr_prev, size_t n,
+                       double* states_out, double* out, int* info) {
+    DkPreamp p;
+    p.init(sr);
+    for (size_t c = 0; c < n; ++c) {
+        const double* s = states + 14 * c;
+        DkState st;
+        st.j_cin = s[0]; st.cin_rhs_prev = s[1];
+        for (int i = 0; i < 8; ++i) st.v[i] = s[2 + i];
+        st.i_nl[0] = s[10]; st.i_nl[1] = s[11]; st.v_nl[0] = s[12]; st.v_nl[1] = s[13];
+        p.g_ldr = g_ldr[c]; p.g_ldr_prev = g_ldr_prev[c];
+        DkStepTrace tr;
+        out[c] = p.dk_step(st, input[c], &tr);
+        double* o = states_out + 14 * c;
+        o[0] = st.j_cin; o[1] = st.cin_rhs_prev;
+        for (int i = 0; i < 8; ++i) o[2 + i] = st.v[i];
+        o[10] = st.i_nl[0]; o[11] = st.i_nl[1]; o[12] = st.v_nl[0]; o[13] = st.v_nl[1];
+        if (info) { info[4 * c] = tr.updates; info[4 * c + 1] = tr.exit_kind; info[4 * c + 2] = tr.clamp_lo; info[4 * c + 3] = tr.clamp_hi; }
+    }
+}
+// R_ldr, g_ldr and g_ldr_prev of the engine's legacy preamp as they stand now (g_ldr_prev: what the NEXT step will use)
+void owo_engine_preamp_ldr(void* e, double* out3) {
+    const DkPreamp& p = ((WurliEngine*)e)->preamp;
+    out3[0] = p.r_ldr; out3[1] = p.g_ldr; out3[2] = p.g_ldr_prev;
+}
+
 // tremolo: n shunt-impedance samples at depth d after Tremolo::new(d, sr); optional osc voltage tap
 void owo_tremolo_stats(unsigned long long* out5) { for (int i = 0; i < 5; ++i) out5[i] = trem_stats()[i]; }
 void owo_tremolo_run(double depth, double sr, double* r_out, size_t n) {

@@ -158,6 +158,12 @@ class OracleEngine:
         self.L.owo_engine_preamp_state(self.h, 1 if shadow else 0, out.ctypes.data_as(C.c_void_p))
         return out
 
+    def preamp_ldr(self):
+        """(r_ldr, g_ldr, g_ldr_prev) of the legacy preamp as they stand now"""
+        out = np.zeros(3, dtype=np.float64)
+        self.L.owo_engine_preamp_ldr(self.h, out.ctypes.data_as(C.c_void_p))
+        return out
+
     def set_r_ulp(self, ulps):
         """test instrumentation: the tremolo's r_ldr moved by `ulps` doubles from now on (another libm's pow / exp / sin)"""
         self.L.owo_engine_set_r_ulp(self.h, int(ulps))
@@ -170,6 +176,32 @@ class OracleEngine:
     def nan_guard_fires(self): return self.L.owo_engine_nan_guard_fires(self.h)
     def slot_state(self, s): return self.L.owo_engine_slot_state(self.h, int(s))
     def slot_note(self, s): return self.L.owo_engine_slot_note(self.h, int(s))
+
+
+DK_EXIT_CONVERGED, DK_EXIT_SINGULAR, DK_EXIT_SIX_UPDATES = 0, 1, 2
+
+
+def dk_step_cases(rate, states, inputs, g_ldr, g_ldr_prev, perturbed=False):
+    """ONE DkPreamp::dk_step (dk_preamp_legacy.rs:447-554) on each of n independent cases at chain rate `rate`: states [n][14] in the
+    preamp_state order.  Returns (states_out [n][14], out [n], info [n][4] = Newton updates, exit (DK_EXIT_*), evaluations clamped at
+    -1 V, at 0.85 V).  perturbed=True: the one-ulp-exp build."""
+    L = lib_perturbed() if perturbed else lib()
+    st = np.ascontiguousarray(states, dtype=np.float64)
+    n = st.shape[0]
+    assert st.shape == (n, 14)
+    x = np.ascontiguousarray(inputs, dtype=np.float64); g = np.ascontiguousarray(g_ldr, dtype=np.float64)
+    gp = np.ascontiguousarray(g_ldr_prev, dtype=np.float64)
+    assert x.shape == (n,) and g.shape == (n,) and gp.shape == (n,)
+    so = np.zeros((n, 14)); out = np.zeros(n); info = np.zeros((n, 4), dtype=np.int32)
+    L.owo_dk_step_cases(C.c_double(rate), _p(st), _p(x), _p(g), _p(gp), C.c_size_t(n), _p(so), _p(out), _p(info))
+    return so, out, info
+
+
+def preamp_dc_nodes(rate, r_ldr):
+    """The eight node voltages of the legacy preamp after set_ldr_resistance(r_ldr); reset() at chain rate `rate` (full_dc_solve at that R)."""
+    v = np.zeros(8)
+    lib().owo_preamp_step(C.c_double(rate), C.c_double(r_ldr), C.c_size_t(0), C.c_double(r_ldr), None, None, C.c_size_t(0), _p(v))
+    return v
 
 
 def render_note(midi, vel, dur, sr):

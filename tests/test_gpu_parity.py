@@ -1046,17 +1046,24 @@ def test_chain_row_is_bit_identical(hiplib, oracle):
     g.close(); c.close()
 
 
+# every dispatch of the legacy preamp's step: k_preamp (lane = (engine, main | shadow)), k_preamp_pair (lane = engine), k_preamp_wide,
+# k_chain_fused, k_chain_row, k_chain_stream
+CHAIN_KERNEL_MODES = {"lane pairs": {"chain_fused": 0, "preamp_wide": 0, "chain_stream": 0, "preamp_pair": 0},
+                      "lane = engine": {"chain_fused": 0, "preamp_wide": 0, "chain_stream": 0, "preamp_pair": 1},
+                      "quad, two launches": {"chain_fused": 0, "preamp_wide": 1},
+                      "quad, fused": {"chain_fused": 1, "chain_row": 0}, "row": {"chain_fused": 1, "chain_row": 1},
+                      "stream": {"chain_fused": 0, "preamp_wide": 0, "chain_stream": 1}}
+
+
 def test_preamp_nan_reset_in_every_chain_kernel(hiplib, oracle):
     """The preamp's OWN NaN reset (dk_preamp_legacy.rs:610-615: `main - shadow` non-finite -> both solver states back to the DC solution at the
     current R_ldr, this sample's output 0.0, the block goes on) cannot be reached through the API; a test hook overwrites a node voltage
     of a solver state with NaN (main of engine 1, shadow of engine 3) or infinity (engine 4, a block later) before a block.  Every chain kernel -- two launches
-    with the lane-pair and the quad-lane preamp, the fused quad chain, the row chain, the stream chain -- must count the same resets and
+    with the lane-pair, the lane = engine and the quad-lane preamp, the fused quad chain, the row chain, the stream chain -- must count the same resets and
     produce the same bits at the preamp tap and the output, in that block and after it; and they are the oracle's (same poke, same block)."""
     import openwurli_amd as ow
     sr, n_eng, length = 48000.0, 5, 96
-    modes = {"lane pairs": {"chain_fused": 0, "preamp_wide": 0, "chain_stream": 0}, "quad, two launches": {"chain_fused": 0, "preamp_wide": 1},
-             "quad, fused": {"chain_fused": 1, "chain_row": 0}, "row": {"chain_fused": 1, "chain_row": 1},
-             "stream": {"chain_fused": 0, "preamp_wide": 0, "chain_stream": 1}}
+    modes = dict(CHAIN_KERNEL_MODES)
     res = {}
     cs = [oracle.OracleEngine(sr) for _ in range(n_eng)]
     for name in list(modes) + ["oracle"]:
@@ -1111,8 +1118,7 @@ def test_preamp_state_rows_are_the_references_fields_in_every_chain_kernel(hipli
     are ~1e-4 A and ~1e-6 A: the same relative bar + 1e-12)."""
     import openwurli_amd as ow
     sr, n_eng = 48000.0, 3
-    modes = {"lane pairs": {"chain_fused": 0, "preamp_wide": 0}, "quad, two launches": {"chain_fused": 0, "preamp_wide": 1},
-             "quad, fused": {"chain_fused": 1, "chain_row": 0}, "row": {"chain_fused": 1, "chain_row": 1}}
+    modes = dict(CHAIN_KERNEL_MODES)
     lens = [64, 97, 512, 1, 33, 256, 128, 512]
     states = {}
     for name in list(modes) + ["oracle"]:
@@ -1161,6 +1167,87 @@ def test_preamp_state_rows_are_the_references_fields_in_every_chain_kernel(hipli
         vnl = np.abs(a[..., 12:14] - o[..., 12:14]) <= 1e-5 * np.abs(o[..., 12:14]) + oracle.ABS_FLOOR_PREAMP
         amps = np.abs(a[..., [0, 1, 10, 11]] - o[..., [0, 1, 10, 11]]) <= 1e-5 * np.abs(o[..., [0, 1, 10, 11]]) + 1e-12
         assert volts.all() and vnl.all() and amps.all(), (b, a - o)
+
+
+def test_finite_preamp_kick_in_every_chain_kernel(hiplib, oracle):
+    """A FINITE kick of a solver state's node voltage through the real dispatch (the NaN test above only ever reaches the DC reset): before
+    block 2, engine 1's main state gets +0.26 mV on BASE1 and engine 4's main state -1.6 mV on OUT (a few Newton updates, back on the
+    trajectory within the block), engine 3's shadow state +6.3 V on COLL1 and engine 2's main state -16 V on EMIT2 (steps that run out of
+    their six updates and sit on the junction clamp: checked here on the oracle's one-step entry).  The kick sizes are the single-step
+    corpus's (tests/dk_step_cases.py).  All six dispatch modes give the same bits at the preamp tap, in both states' rows and at the
+    output, in the kicked block and after it.  Against the oracle (same kicks): the engines whose kick the reference algorithm itself
+    reconverges from -- the one-ulp-exp oracle stays within the usual bars of the unperturbed one from the kick on; decided on the CPU --
+    at ABS_FLOOR_OUTPUT / ABS_FLOOR_PREAMP; engine 0 is never kicked."""
+    import dk_step_cases as dk
+    import openwurli_amd as ow
+    sr, n_eng, length, n_blocks = 48000.0, 5, 96, 6
+    kicks = [(1, False, 0, dk.KICK_MAGS[6]), (4, False, 6, -dk.KICK_MAGS[8]), (3, True, 2, dk.KICK_MAGS[17]), (2, False, 3, -dk.KICK_MAGS[18])]
+    res, six = {}, {}
+    for name in list(CHAIN_KERNEL_MODES) + ["oracle", "oracle, one-ulp exp"]:
+        g = None
+        if name in CHAIN_KERNEL_MODES:
+            g = ow.EnginePool(sr, n_eng); g.set_sample_rate(sr)
+            for k, v in CHAIN_KERNEL_MODES[name].items():
+                g.set_switch(k, v)
+            es = [g[k] for k in range(n_eng)]
+        else:
+            es = [oracle.OracleEngine(sr, perturbed=name != "oracle") for _ in range(n_eng)]
+            for e in es:
+                e.set_sample_rate(sr)
+        for k, e in enumerate(es):
+            e.set_tremolo_depth(0.2 * k); e.set_volume(0.5)
+            for note in (45 + k, 60, 67 + k):
+                e.note_on(note, 0.8)
+        outs, pres, rows = [], [], []
+        for b in range(n_blocks):
+            if b == 2:
+                for k, shadow, node, dv in kicks:
+                    now = es[k].read_preamp_state(shadow) if g is not None else es[k].preamp_state(shadow)[:14]
+                    es[k].poke_preamp_node(node, float(now[2 + node] + dv), shadow=shadow)
+                    if name == "oracle":      # what the kicked state's next step does, by the one-step entry
+                        st = es[k].preamp_state(shadow)[:14]
+                        gl = es[k].preamp_ldr()[1]
+                        x = dk.last_input(2.0 * sr, st) if not shadow else 0.0
+                        six[k] = oracle.dk_step_cases(2.0 * sr, st[None, :], np.array([x]), np.array([gl]), np.array([gl]))[2][0]
+            if g is not None:
+                outs.append(g.render(length).copy()); pres.append(g.preamp_out(2 * length).copy())
+                rows.append(np.stack([np.stack([e.read_preamp_state(False), e.read_preamp_state(True)]) for e in es]))
+            else:
+                taps = [e.render_taps(length) for e in es]
+                outs.append(np.stack([t[0] for t in taps])); pres.append(np.stack([t[2] for t in taps]))
+                rows.append(None)
+        resets = [es[k].diag().preamp_nan_resets for k in range(n_eng)] if g is not None else None
+        res[name] = (outs, pres, rows, resets)
+        if g is not None:
+            g.close()
+        else:
+            for e in es:
+                e.close()
+    assert six[3][1] == oracle.DK_EXIT_SIX_UPDATES and six[2][1] == oracle.DK_EXIT_SIX_UPDATES, six       # the large kicks do run out of updates
+    assert six[1][1] == oracle.DK_EXIT_CONVERGED and six[4][1] == oracle.DK_EXIT_CONVERGED and six[1][0] >= 1, six
+    ref = res["lane pairs"]
+    assert ref[3] == [0] * n_eng, ref[3]                         # a finite kick is not a reset
+    for name in CHAIN_KERNEL_MODES:
+        assert res[name][3] == ref[3], (name, res[name][3])
+        for b in range(n_blocks):
+            assert res[name][1][b].tobytes() == ref[1][b].tobytes(), (name, b, "preamp tap")
+            assert res[name][2][b].tobytes() == ref[2][b].tobytes(), (name, b, "preamp state rows")
+            assert res[name][0][b].tobytes() == ref[0][b].tobytes(), (name, b, "output")
+            assert np.all(np.isfinite(res[name][0][b]))
+    cpu, cpu_p = res["oracle"], res["oracle, one-ulp exp"]
+
+    def within(a, o, k):
+        return all(oracle.parity_report(a[0][b][k], o[0][b][k], abs_floor=oracle.ABS_FLOOR_OUTPUT)["n_bad"] == 0 and
+                   oracle.parity_report(a[1][b][k], o[1][b][k], abs_floor=oracle.ABS_FLOOR_PREAMP)["n_bad"] == 0 for b in range(n_blocks))
+
+    reconverging = [k for k in range(n_eng) if within(cpu_p, cpu, k)]
+    assert 0 in reconverging and 1 in reconverging and 4 in reconverging, reconverging      # the small kicks: the reference pins them
+    for k in reconverging:
+        for b in range(n_blocks):
+            rep = oracle.parity_report(ref[0][b][k], cpu[0][b][k], abs_floor=oracle.ABS_FLOOR_OUTPUT)
+            assert rep["n_bad"] == 0, (k, b, "output", rep)
+            rep = oracle.parity_report(ref[1][b][k], cpu[1][b][k], abs_floor=oracle.ABS_FLOOR_PREAMP)
+            assert rep["n_bad"] == 0, (k, b, "preamp tap", rep)
 
 
 def test_post_pair_is_bit_identical(hiplib):

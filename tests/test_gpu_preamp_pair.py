@@ -124,6 +124,31 @@ def test_preamp_pair_nan_reset(hiplib):
         assert np.all(np.isfinite(o))
 
 
+def test_preamp_pair_finite_kicks(hiplib):
+    """Finite kicks of node voltages (sizes from the single-step corpus, tests/dk_step_cases.py: microvolts to tens of volts), main states
+    and shadow states, on engines spread over the wavefronts of both kernels: in k_preamp a kicked state's wavefront iterates with its 63
+    neighbours, in k_preamp_pair with the other state of its own lane too.  Same bits in the kicked block and after it; no reset counted."""
+    import dk_step_cases as dk
+    import openwurli_amd as ow
+    sr, n_eng, length = 48000.0, 200, 96
+
+    def kick(g):
+        for i, dv in enumerate(dk.KICK_MAGS):
+            k = (i * 37 + 3) % n_eng
+            for shadow, sign in ((False, 1.0), (True, -1.0)) if i % 2 else ((True, 1.0),):
+                now = g[k].read_preamp_state(shadow)
+                g[k].poke_preamp_node(i % 8, float(now[2 + i % 8] + sign * dv), shadow=shadow)
+
+    res = {}
+    for pair in (0, 1):
+        res[pair] = _run(ow, sr, n_eng, pair, [length] * 5, {2: kick})
+    _same(res[0], res[1], "finite kicks")
+    assert all(d == (0, 0) for d in res[1][3]), res[1][3]
+    assert res[1][2][2].tobytes() != res[1][2][1].tobytes()
+    for o in res[1][0]:
+        assert np.all(np.isfinite(o))
+
+
 def test_preamp_pair_default_threshold(hiplib):
     """The switch: -1 (default) picks the pair kernel from 131 072 engines; 0 / 1 force it; only those three values."""
     import openwurli_amd as ow
