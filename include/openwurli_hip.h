@@ -30,10 +30,10 @@ typedef struct ow_engine ow_engine;
 
 /* Version of this header's struct layouts and signatures.  ow_abi_version() returns the value the library was built with; a binding
  * checks it once after loading.  The by-pointer configuration structs (ow_batch_cfg, ow_midi_render_cfg) additionally carry their own
- * size in their first field, and ow_batch_cfg / ow_calibrate_cfg / ow_preamp_measure_cfg the size of one ow_job / ow_calib_point / ow_preamp_point: a caller built
+ * size in their first field, and ow_batch_cfg / ow_calibrate_cfg / ow_preamp_measure_cfg / ow_poly_cfg the size of one ow_job / ow_calib_point / ow_preamp_point / ow_poly_chord: a caller built
  * against another header is refused ("ABI mismatch",
  * negative return) instead of having fields read past the end of what it passed. */
-#define OW_ABI_VERSION 6
+#define OW_ABI_VERSION 7
 int ow_abi_version(void);
 
 /* VoiceState, crates/openwurli-dsp/src/engine.rs:30-37 */
@@ -405,6 +405,52 @@ typedef struct ow_preamp_measure_row {
  * a short trace_stride, a device error). */
 int ow_preamp_measure(const ow_preamp_point* points, size_t n, const ow_preamp_measure_cfg* cfg, ow_preamp_measure_row* rows_out,
                       double* trace_out, size_t trace_stride);
+
+/* ---- chord intermodulation (`preamp-bench render-poly`, tools/preamp-bench/src/main.rs:1397-1592) --------------------------- */
+/* One chord.  Voice i is Voice::note_on(notes[i], velocities[i] / 127, 44100, notes[i] * 2654435761 + i (u32 wrapping), mlp = true)
+ * (:1435-1440).  The voices' sum goes through ONE chain (`final`), every voice through a chain of its OWN, added in voice order
+ * (`separate_sum`); residual = final - separate_sum is what the shared preamp, power amp and speaker intermodulate (:1460-1513).  A
+ * chain is a fresh legacy DkPreamp at 88 200 Hz, set_ldr_resistance(r_ldr) (clamp to 1 kohm, 0.01 ohm hysteresis against new()'s
+ * 1 Mohm) and THEN reset() -- so the DC solve runs at the chord's --ldr, the opposite order of `render` / ow_batch_render --, per-sample
+ * 2x oversampling (:961-974), x volume^2, PowerAmp::new() at the base rate unless no_poweramp, Speaker(speaker), x POST_SPEAKER_GAIN. */
+#define OW_POLY_MAX_NOTES 31        /* a chord's n + 1 chains fit one wavefront in either lane layout */
+typedef struct ow_poly_chord {
+    uint8_t n_notes;                       /* 1..OW_POLY_MAX_NOTES */
+    uint8_t no_poweramp;                   /* --no-poweramp */
+    uint8_t reserved[6];
+    uint8_t notes[32], velocities[32];     /* --notes (33..96) / --velocities (0..127; velocity = byte / 127), already padded to n_notes (:1410-1420) */
+    double volume, speaker, r_ldr;         /* --volume (applied squared), --speaker, --ldr */
+} ow_poly_chord;
+typedef struct ow_poly_cfg {
+    uint32_t struct_size;  /* = sizeof(ow_poly_cfg) of the caller's header */
+    uint32_t chord_size;   /* = sizeof(ow_poly_chord) of the caller's header (the stride of `chords`) */
+    double duration_s;     /* --duration (default 3.0); every chord renders (duration_s * 44100.0) as usize samples */
+    int device;
+    int preamp_kind;       /* OW_PREAMP_LEGACY8 only (below) */
+    int power_amp_kind;    /* OW_POWER_AMP_BEHAVIORAL only (below) */
+    int reserved;
+} ow_poly_cfg;
+/* Index 0 / 1 / 2 of the arrays: the shared chain (poly), the separate chains' sum, the residual.  Window = samples
+ * [8820, min(88200, n)) (:1516-1517). */
+typedef struct ow_poly_row {
+    double peak;                           /* peak_abs(final_output), whole render (:1530) */
+    double residual_peak;                  /* peak_abs(residual), whole render (:1543) */
+    double win_peak[3], win_mean_sq[3];    /* poly, separate, residual: linear values */
+    double peak_db[3], rms_db[3];          /* peak_db / rms_db (:916-927) with their -120 floors */
+    double intermod_ratio_db;              /* rms_db[0] - rms_db[2] (:1575) */
+} ow_poly_row;
+/* cmd_render_poly for n_chords chords at once, 44.1 kHz.  rows_out: [n_chords].  final_out / separate_sum_out / residual_out: each NULL
+ * or a host f64 array [n_chords][stride >= samples per chord]; which of them are asked for changes no number.  Large grids run in chunks
+ * of a fixed device-memory budget (a chord takes n_notes voice rows plus three result rows; OW_POLY_CHUNK=<chords> caps a chunk; tests
+ * use it).  A chord's numbers do not depend on the other chords of the call.
+ * Returns the samples per chord, <0 on error.  Refused before any device work (ow_last_error says why): "ABI mismatch", n_notes of 0 or
+ * above OW_POLY_MAX_NOTES, a note outside 33..96, a velocity above 127, a non-finite or non-positive r_ldr, a non-finite volume or
+ * speaker, a duration of 8820 samples or fewer (the reference's window slice panics there), a short stride, and two follow-ups:
+ *   - OW_PREAMP_MELANGE12: the melange adapter's reset() re-clones the settled state AFTER set_ldr_resistance and so silently discards
+ *     --ldr (melange_adapter.rs:83-93); what the command then measures needs a decision of its own;
+ *   - OW_POWER_AMP_MELANGE: the 7-BJT solver runs as its own launch between the preamp and the speaker stage (as in ow_batch_render). */
+long long ow_render_poly(const ow_poly_chord* chords, size_t n_chords, const ow_poly_cfg* cfg, ow_poly_row* rows_out,
+                         double* final_out, double* separate_sum_out, double* residual_out, size_t stride);
 
 #ifdef __cplusplus
 }

@@ -38,7 +38,7 @@ class OwMidiEvent(C.Structure):
 MIDI_DTYPE = [("engine", "<u4"), ("type", "u1"), ("note", "u1"), ("reserved", "<u2"), ("value", "<f4")]
 
 
-ABI_VERSION = 6      # include/openwurli_hip.h OW_ABI_VERSION; load_library() checks it against ow_abi_version()
+ABI_VERSION = 7      # include/openwurli_hip.h OW_ABI_VERSION; load_library() checks it against ow_abi_version()
 
 
 class OwBatchCfg(C.Structure):
@@ -124,6 +124,27 @@ PBENCH_GAIN_LO = 13230   # OW_PBENCH_GAIN_LO
 PBENCH_HARM_LO = 16537   # OW_PBENCH_HARM_LO
 
 
+POLY_MAX_NOTES = 31      # include/openwurli_hip.h OW_POLY_MAX_NOTES
+
+
+class OwPolyChord(C.Structure):
+    _fields_ = [("n_notes", C.c_uint8), ("no_poweramp", C.c_uint8), ("reserved", C.c_uint8 * 6), ("notes", C.c_uint8 * 32),
+                ("velocities", C.c_uint8 * 32), ("volume", C.c_double), ("speaker", C.c_double), ("r_ldr", C.c_double)]
+
+
+class OwPolyCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("chord_size", C.c_uint32), ("duration_s", C.c_double), ("device", C.c_int),
+                ("preamp_kind", C.c_int), ("power_amp_kind", C.c_int), ("reserved", C.c_int)]
+
+    def __init__(self, duration_s=3.0, device=0, preamp_kind=0, power_amp_kind=0):
+        super().__init__(C.sizeof(OwPolyCfg), C.sizeof(OwPolyChord), duration_s, device, preamp_kind, power_amp_kind, 0)
+
+
+class OwPolyRow(C.Structure):
+    _fields_ = [("peak", C.c_double), ("residual_peak", C.c_double), ("win_peak", C.c_double * 3), ("win_mean_sq", C.c_double * 3),
+                ("peak_db", C.c_double * 3), ("rms_db", C.c_double * 3), ("intermod_ratio_db", C.c_double)]
+
+
 # every symbol include/openwurli_hip.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 class OwSegment(C.Structure):
@@ -205,6 +226,7 @@ SYMBOLS = {
     "ow_render_midi": (C.c_longlong, [_VP, _VP, C.c_size_t, _VP, _VP, C.c_size_t, _VP]),
     "ow_calibrate": (C.c_int, [_VP, C.c_size_t, C.POINTER(OwCalibrateCfg), _VP, _VP, C.c_size_t]),
     "ow_preamp_measure": (C.c_int, [_VP, C.c_size_t, C.POINTER(OwPreampMeasureCfg), _VP, _VP, C.c_size_t]),
+    "ow_render_poly": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwPolyCfg), _VP, _VP, _VP, _VP, C.c_size_t]),
 }
 
 
