@@ -60,6 +60,15 @@ int ow_debug_unary(int which, const double* x, size_t n, double* fast, double* l
  * not fill the last one.  Returns 0, <0 on error. */
 int ow_debug_dk_step(int form, double rate, const double* states_in, const double* input, const double* g_ldr, const double* g_ldr_prev, size_t n,
                      double* states_out, double* out, int device);
+/* ONE step of the Twin-T tremolo oscillator (TremCircuit::process_sample(0.0), gen_tremolo.rs:2353-3116) on n independent cases at chain
+ * rate `rate`, through one of the kernels' three forms of it: form 0 = trem_osc_step, one system per lane, TremPark / TremMats in LDS as
+ * k_tremolo sets them up (64 cases per wavefront); 1 = trem_osc_step_wide, four lanes per system (k_tremolo_wide, k_trem_traj_extend: 16
+ * cases per wavefront); 2 = trem_osc_step_row, sixteen lanes per system with its generic-sweep and backward-Euler wrappers
+ * (k_trem_settle_row, k_trem_traj_extend_row: one case per wavefront).  The production device functions with the production constants of
+ * that rate; the CdS cell (env, r_ldr) is not stepped.  states_in / states_out: [n][15] = v_prev[7], i_nl_prev[4], i_nl_prev_prev[4] (the
+ * first fifteen of ow_debug_trem_trajectory's state rows); out: [n] = the step's return value, v[OUT]; info: [n] = the step's increment of
+ * the backward-Euler fallback counter.  Cases fill the wavefronts in order; n need not fill the last one.  Returns 0, <0 on error. */
+int ow_debug_trem_step(int form, double rate, const double* states_in, size_t n, double* states_out, double* out, unsigned long long* info, int device);
 
 /* ---- tremolo phase groups -------------------------------------------------------------------- */
 /* Engines whose tremolo oscillators are bit-identical share one oscillator (a fresh pool is one group).  This hook cuts the pool into

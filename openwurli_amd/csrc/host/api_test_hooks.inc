@@ -532,4 +532,48 @@ int ow_debug_dk_step(int form, double rate, const double* states_in, const doubl
         return 0;
     } catch (const std::exception& ex) { set_err(std::string("ow_debug_dk_step: ") + ex.what()); return -1; }
 }
+
+int ow_debug_trem_step(int form, double rate, const double* states_in, size_t n, double* states_out, double* out, unsigned long long* info, int device) {
+    try {
+        if (!states_in || !states_out || !out || !info || form < 0 || form > 2 || !(rate > 0.0)) throw std::runtime_error("bad argument");
+        if (n == 0) return 0;
+        if (n > (size_t)1 << 22) throw std::runtime_error("too many cases");
+        HIP_OK(hipSetDevice(device));
+        std::unique_ptr<OwConsts> hc(new OwConsts());
+        // build_consts takes the HOST rate; a host rate >= 88.2 kHz runs the chain at that rate without oversampling (engine.rs:195)
+        owhip::build_consts(*hc, rate < 88200.0 ? rate * 0.5 : rate, OW_PREAMP_LEGACY8);
+        if (hc->os_sr != rate) throw std::runtime_error("rate is not reachable as a chain rate");
+        // the eighteen tremolo rows: [field][case] for the lane and quad forms, [case][field] for the row form; cell at rest, counter 0
+        const bool by_case = form == 2;
+        auto at = [&](size_t f, size_t c) { return by_case ? c * 18 + f : f * n + c; };
+        std::vector<double> rows(18 * n, 0.0);
+        for (size_t c = 0; c < n; ++c) {
+            for (size_t f = 0; f < 15; ++f) rows[at(f, c)] = states_in[c * 15 + f];
+            rows[at(CS_T_RLDR, c)] = 1000000.0;
+        }
+        DevMem dK, dIn, dOut, dO, dI;
+        dK.alloc(sizeof(OwConsts)); dIn.alloc(sizeof(double) * 18 * n); dOut.alloc(sizeof(double) * 18 * n);
+        dO.alloc(sizeof(double) * n); dI.alloc(sizeof(unsigned long long) * n);
+        HIP_OK(hipMemcpy(dK.p, hc.get(), sizeof(OwConsts), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dIn.p, rows.data(), sizeof(double) * 18 * n, hipMemcpyHostToDevice));
+        HIP_OK(hipMemset(dOut.p, 0, sizeof(double) * 18 * n));
+        HIP_OK(hipMemset(dO.p, 0, sizeof(double) * n));
+        HIP_OK(hipMemset(dI.p, 0, sizeof(unsigned long long) * n));
+        const size_t per_wave[3] = {64, 16, 1};                  // cases of one wavefront: lane | quad | the whole wavefront
+        const dim3 grid((unsigned)((n + per_wave[form] - 1) / per_wave[form])), block(64);
+        const OwConsts* K = dK.as<OwConsts>();
+        switch (form) {
+            case 0: owdev::k_debug_trem_step<owdev::TSF_LANE><<<grid, block>>>(K, dIn.as<double>(), (int)n, dOut.as<double>(), dO.as<double>(), dI.as<unsigned long long>()); break;
+            case 1: owdev::k_debug_trem_step<owdev::TSF_WIDE><<<grid, block>>>(K, dIn.as<double>(), (int)n, dOut.as<double>(), dO.as<double>(), dI.as<unsigned long long>()); break;
+            default: owdev::k_debug_trem_step<owdev::TSF_ROW><<<grid, block>>>(K, dIn.as<double>(), (int)n, dOut.as<double>(), dO.as<double>(), dI.as<unsigned long long>()); break;
+        }
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpy(rows.data(), dOut.p, sizeof(double) * 18 * n, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(out, dO.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(info, dI.p, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+        for (size_t c = 0; c < n; ++c)
+            for (size_t f = 0; f < 15; ++f) states_out[c * 15 + f] = rows[at(f, c)];
+        return 0;
+    } catch (const std::exception& ex) { (void)hipGetLastError(); set_err(std::string("ow_debug_trem_step: ") + ex.what()); return -1; }
+}
 }  // extern "C"

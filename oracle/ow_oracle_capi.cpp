@@ -414,6 +414,61 @@ void owo_tremolo_matrices(double sr, double* s, double* k, double* sni, double* 
     for (int i = 0; i < 7; ++i) for (int j = 0; j < 4; ++j) sni[i * 4 + j] = c.s_ni[i][j];
 }
 double owo_fast_exp(double x) { return fast_exp(x); }
+// The same circuit run on as a recurrence, for harvesting states: from state_in [15] (NULL: as init_default(); set_sample_rate(rate) leaves
+// it -- DC_OP after the warm-up, where Tremolo::new's settle starts) take n steps and store the state in front of every `every`-th step:
+// states_out [(n + every - 1) / every][15].
+void owo_trem_harvest(double rate, const double* state_in, size_t n, size_t every, double* states_out) {
+    TremCircuit* c = new TremCircuit();
+    c->init_default();
+    c->set_sample_rate(rate);
+    if (state_in) {
+        for (int i = 0; i < TN; ++i) c->v_prev[i] = state_in[i];
+        for (int i = 0; i < TM; ++i) { c->i_nl_prev[i] = state_in[7 + i]; c->i_nl_prev_prev[i] = state_in[11 + i]; }
+        c->input_prev = 0.0;
+    }
+    for (size_t k = 0; k < n; ++k) {
+        if (k % every == 0) {
+            double* o = states_out + 15 * (k / every);
+            for (int i = 0; i < TN; ++i) o[i] = c->v_prev[i];
+            for (int i = 0; i < TM; ++i) { o[7 + i] = c->i_nl_prev[i]; o[11 + i] = c->i_nl_prev_prev[i]; }
+        }
+        c->process_sample(0.0);
+    }
+    delete c;
+}
+// TremCircuit::process_sample(0.0) as a pure function of n independent cases at chain rate `rate` (tests/trem_step_cases.py): the circuit
+// after init_default(); set_sample_rate(rate), input_prev = 0, each case's state [15] = v_prev[7], i_nl_prev[4], i_nl_prev_prev[4] put in
+// and ONE step taken.  states_out [n][15], out [n] = the step's return value, info [n][10] (TremStepTrace): iteration index at which the
+// trapezoidal solve converged (50 = exhausted), backward-Euler retry taken, its iteration index (50 = exhausted), the kept solve converged,
+// NaN reset, sweeps with a row exchange, singular sweeps, sweeps in which pnjlim's logarithm ran, sweeps in which the 3.5 V cap fired, sweeps in which a port's step exceeded the limiter's 1e-4 V
+// threshold.
+// log_ulp: the result of pnjlim's std::log moved by that many doubles for the duration of this call (0: std::log itself).
+void owo_trem_step_cases(double rate, const double* states, size_t n, int log_ulp, double* states_out, double* out, int* info) {
+    TremCircuit* c = new TremCircuit();
+    c->init_default();
+    c->set_sample_rate(rate);
+    trem_log_ulp() = log_ulp;
+    for (size_t k = 0; k < n; ++k) {
+        const double* s = states + 15 * k;
+        for (int i = 0; i < TN; ++i) c->v_prev[i] = s[i];
+        for (int i = 0; i < TM; ++i) { c->i_nl_prev[i] = s[7 + i]; c->i_nl_prev_prev[i] = s[11 + i]; }
+        c->input_prev = 0.0;
+        TremStepTrace tr;
+        trem_trace() = &tr;
+        out[k] = c->process_sample(0.0);
+        trem_trace() = nullptr;
+        double* o = states_out + 15 * k;
+        for (int i = 0; i < TN; ++i) o[i] = c->v_prev[i];
+        for (int i = 0; i < TM; ++i) { o[7 + i] = c->i_nl_prev[i]; o[11 + i] = c->i_nl_prev_prev[i]; }
+        if (info) {
+            int* f = info + 10 * k;
+            f[0] = tr.trap_iter; f[1] = tr.be_taken; f[2] = tr.be_iter; f[3] = tr.converged; f[4] = tr.nan_reset;
+            f[5] = tr.pivot_sweeps; f[6] = tr.singular_sweeps; f[7] = tr.log_sweeps; f[8] = tr.cap_sweeps; f[9] = tr.thr_sweeps;
+        }
+    }
+    trem_log_ulp() = 0;
+    delete c;
+}
 
 // melange 12-node preamp (main - shadow) run: per-sample input x[n], R_ldr r[n] (null -> untouched 100 kOhm nominal)
 void owo_melange_run(double sr, const double* x, const double* r, double* y, size_t n) {

@@ -17,6 +17,28 @@
 namespace owo {
 // Newton sweeps and row exchanges per column of the Twin-T solver since process start (statistics for the GPU mapping, test infrastructure)
 inline unsigned long long* trem_stats() { static thread_local unsigned long long v[5] = {0, 0, 0, 0, 0}; return v; }
+// Test instrumentation of TremCircuit::process_sample (owo_trem_step_cases): how one step's solver went.  Observes, changes nothing.
+struct TremStepTrace {
+    int trap_iter = 0;      // iteration index at which the trapezoidal solve converged (0..49), 50 = its sweeps were exhausted
+    int be_taken = 0;       // the backward-Euler retry ran
+    int be_iter = 0;        // ... and converged at this iteration index (50 = exhausted too)
+    int converged = 0;      // the solve whose result the step keeps converged
+    int nan_reset = 0;      // the step ended in the reset to DC_OP
+    int pivot_sweeps = 0, singular_sweeps = 0, log_sweeps = 0, cap_sweeps = 0, thr_sweeps = 0;      // sweeps (of either solve) with a row exchange /
+                            // a singular Jacobian / a pnjlim logarithm / the 3.5 V cap / a port step above the limiter's 1e-4 V threshold
+    bool saw_log = false;   // (scratch: a logarithm ran since the sweep began)
+};
+inline TremStepTrace*& trem_trace() { static thread_local TremStepTrace* t = nullptr; return t; }
+// Test instrumentation: the result of pnjlim's std::log moved by this many doubles (what another libm does to it).  Thread-local, 0 unless
+// owo_trem_step_cases sets it for the duration of its call: no other entry of the oracle sees anything but std::log.
+inline int& trem_log_ulp() { static thread_local int k = 0; return k; }
+inline double trem_log(double x) {
+    double y = std::log(x);
+    if (TremStepTrace* t = trem_trace()) t->saw_log = true;
+    for (int k = trem_log_ulp(); k > 0; --k) y = std::nextafter(y, INFINITY);
+    for (int k = trem_log_ulp(); k < 0; ++k) y = std::nextafter(y, -INFINITY);
+    return y;
+}
 
 
 // gen_tremolo.rs:1140-1166
@@ -45,10 +67,10 @@ inline double pnjlim(double vnew, double vold, double vt, double vcrit) {
     if (vnew > vcrit && std::fabs(vnew - vold) > vt + vt) {
         if (vold >= 0.0) {
             const double arg = 1.0 + (vnew - vold) / vt;
-            if (arg > 0.0) return vold + vt * std::log(arg);
+            if (arg > 0.0) return vold + vt * trem_log(arg);
             return vcrit;
         }
-        return vt * std::log(vnew / vt);
+        return vt * trem_log(vnew / vt);
     }
     return vnew;
 }
@@ -260,6 +282,9 @@ struct TremCircuit {
             double b[4] = {f0, f1, f2, f3};
             bool singular = false;
             trem_stats()[0] += 1;
+            TremStepTrace* const tr = trem_trace();
+            bool tr_pivot = false, tr_cap = false, tr_thr = false;
+            if (tr) tr->saw_log = false;
             for (int col = 0; col < 4; ++col) {
                 int max_row = col;
                 double max_val = std::fabs(a[col][col]);
@@ -268,6 +293,7 @@ struct TremCircuit {
                 if (max_val < 1e-15) { singular = true; break; }
                 if (max_row != col) {
                     trem_stats()[1 + col] += 1;
+                    tr_pivot = true;
                     for (int j = 0; j < 4; ++j) std::swap(a[col][j], a[max_row][j]);
                     std::swap(b[col], b[max_row]);
                 }
@@ -298,6 +324,7 @@ struct TremCircuit {
                     const double v_trial = p[q] + kk[q][0] * i_trial[0] + kk[q][1] * i_trial[1] + kk[q][2] * i_trial[2] + kk[q][3] * i_trial[3];
                     dv_trial[q] = v_trial - vd[q];
                     v_lim[q] = (std::fabs(dv_trial[q]) > 1e-4) ? pnjlim(v_trial, vd[q], vts[q], vcr[q]) : v_trial;
+                    if (std::fabs(dv_trial[q]) > 1e-4) tr_thr = true;
                 }
                 bool any_limited = false;
                 double global_alpha = 1.0;
@@ -311,9 +338,10 @@ struct TremCircuit {
                 {
                     const double max_dv = std::fmax(std::fmax(std::fmax(std::fabs(dv_trial[0] * global_alpha), std::fabs(dv_trial[1] * global_alpha)),
                                                               std::fabs(dv_trial[2] * global_alpha)), std::fabs(dv_trial[3] * global_alpha));
-                    if (max_dv > 3.5) { global_alpha *= std::fmax(3.5 / max_dv, 0.1); any_limited = true; }
+                    if (max_dv > 3.5) { global_alpha *= std::fmax(3.5 / max_dv, 0.1); any_limited = true; tr_cap = true; }
                 }
                 for (int q = 0; q < 4; ++q) i_nl[q] -= global_alpha * delta[q];
+                if (tr) { tr->pivot_sweeps += tr_pivot; tr->log_sweeps += tr->saw_log; tr->cap_sweeps += tr_cap; tr->thr_sweeps += tr_thr; }
                 if (!any_limited) {
                     bool conv = true;
                     for (int q = 0; q < 4; ++q) {
@@ -332,6 +360,7 @@ struct TremCircuit {
                 bool any_limited = false;
                 for (int q = 0; q < 4; ++q) {
                     if (std::fabs(dv[q]) > 1e-4) {
+                        tr_thr = true;
                         const double vl = pnjlim(vd[q] + dv[q], vd[q], vts[q], vcr[q]);
                         const double ratio = std::fmax((vl - vd[q]) / dv[q], 0.01);
                         if (ratio < alpha[q]) { alpha[q] = ratio; if (ratio < 1.0) any_limited = true; }
@@ -344,8 +373,10 @@ struct TremCircuit {
                 if (max_dv > 3.5) {
                     const double factor = std::fmax(3.5 / max_dv, 0.1);
                     for (int q = 0; q < 4; ++q) alpha[q] *= factor;
+                    tr_cap = true;
                 }
                 for (int q = 0; q < 4; ++q) i_nl[q] -= alpha[q] * delta[q];
+                if (tr) { tr->pivot_sweeps += tr_pivot; tr->log_sweeps += tr->saw_log; tr->cap_sweeps += tr_cap; tr->thr_sweeps += tr_thr; }
                 if (!any_limited) {
                     bool conv = true;
                     for (int q = 0; q < 4; ++q) {
@@ -357,6 +388,7 @@ struct TremCircuit {
                     if (conv) { iters_out = (uint32_t)iter; return true; }
                 }
             } else {
+                if (tr) { tr->pivot_sweeps += tr_pivot; tr->singular_sweeps += 1; }
                 const double f[4] = {f0, f1, f2, f3};
                 for (int q = 0; q < 4; ++q) {
                     const double cl = be ? 0.01 : std::fmax(std::fabs(i_nl[q]) * 0.1, 0.01);
@@ -420,6 +452,7 @@ struct TremCircuit {
         last_nr_iterations = TREM_MAX_ITER;
         uint32_t it = 0;
         if (nr_solve(p, k, i_nl, false, it)) last_nr_iterations = it;
+        if (TremStepTrace* tr = trem_trace()) { tr->trap_iter = (int)last_nr_iterations; tr->converged = last_nr_iterations < (uint32_t)TREM_MAX_ITER; }
 
         double v[TN];
         for (int i = 0; i < TN; ++i) {
@@ -452,6 +485,7 @@ struct TremCircuit {
             }
             for (int i = 0; i < TM; ++i) i_nl[i] = 2.0 * i_nl_prev[i] - i_nl_prev_prev[i];
             if (nr_solve(p_be, k_be, i_nl, true, it)) last_nr_iterations = it;
+            if (TremStepTrace* tr = trem_trace()) { tr->be_taken = 1; tr->be_iter = (int)last_nr_iterations; tr->converged = last_nr_iterations < (uint32_t)TREM_MAX_ITER; }
             for (int i = 0; i < TN; ++i) {
                 v[i] = v_pred_be[i];
                 for (int j = 0; j < TM; ++j) v[i] += s_ni_be[i][j] * i_nl[j];
@@ -464,6 +498,7 @@ struct TremCircuit {
             for (int i = 0; i < TM; ++i) { i_nl_prev[i] = TREM_DC_NL_I[i]; i_nl_prev_prev[i] = TREM_DC_NL_I[i]; }
             input_prev = 0.0;
             diag_nan_reset_count += 1;
+            if (TremStepTrace* tr = trem_trace()) tr->nan_reset = 1;
             return 4.26480458363572357e0;
         }
         for (int i = 0; i < TN; ++i) v_prev[i] = v[i];

@@ -197,6 +197,33 @@ def dk_step_cases(rate, states, inputs, g_ldr, g_ldr_prev, perturbed=False):
     return so, out, info
 
 
+TREM_INFO = ("trap_iter", "be_taken", "be_iter", "converged", "nan_reset", "pivot_sweeps", "singular_sweeps", "log_sweeps", "cap_sweeps", "thr_sweeps")
+
+
+def trem_step_cases(rate, states, log_ulp=0):
+    """ONE TremCircuit::process_sample(0.0) (gen_tremolo.rs:2353-3116) on each of n independent cases at chain rate `rate`: states [n][15] =
+    v_prev[7], i_nl_prev[4], i_nl_prev_prev[4].  Returns (states_out [n][15], out [n], info [n][10] in the order of TREM_INFO: iteration
+    index at which the trapezoidal solve converged (50 = exhausted), retry taken, its iteration index, the kept solve converged, NaN
+    reset, sweeps with a row exchange / a singular Jacobian / a pnjlim logarithm / the 3.5 V cap / a port step above the limiter's 1e-4 V threshold).  log_ulp: pnjlim's logarithm moved by
+    that many doubles (what another libm does to it)."""
+    st = np.ascontiguousarray(states, dtype=np.float64)
+    n = st.shape[0]
+    assert st.shape == (n, 15)
+    so = np.zeros((n, 15)); out = np.zeros(n); info = np.zeros((n, 10), dtype=np.int32)
+    lib().owo_trem_step_cases(C.c_double(rate), _p(st), C.c_size_t(n), C.c_int(int(log_ulp)), _p(so), _p(out), _p(info))
+    return so, out, info
+
+
+def trem_harvest(rate, n, every, state=None):
+    """States [ceil(n / every)][15] in front of every `every`-th of n consecutive oscillator steps at chain rate `rate`, from `state` or (None)
+    from the circuit as init_default(); set_sample_rate(rate) leaves it (DC_OP after the warm-up: where Tremolo::new's settle starts)."""
+    m = (int(n) + int(every) - 1) // int(every)
+    out = np.zeros((m, 15))
+    st = None if state is None else _p(np.ascontiguousarray(state, dtype=np.float64))
+    lib().owo_trem_harvest(C.c_double(rate), st, C.c_size_t(int(n)), C.c_size_t(int(every)), _p(out))
+    return out
+
+
 def preamp_dc_nodes(rate, r_ldr):
     """The eight node voltages of the legacy preamp after set_ldr_resistance(r_ldr); reset() at chain rate `rate` (full_dc_solve at that R)."""
     v = np.zeros(8)
@@ -335,6 +362,15 @@ ABS_FLOOR_MELANGE_OUTPUT = 1.5e-6
 ABS_FLOOR_MELANGE_LIT_PREAMP = 3.4e-8
 ABS_FLOOR_MELANGE_LIT_OUTPUT = 3.4e-8
 
+# single steps of the Twin-T oscillator (tests/trem_step_cases.py, tests/test_gpu_trem_step.py): state rows are held to 1e-5 relative plus
+# these.  The only operation of the step that is not IEEE arithmetic is pnjlim's logarithm; with its result moved to the neighbouring
+# double either way, the oracle's step -- on the finite cases that keep their exits (retry taken or not, converged or exhausted, reset) --
+# leaves the relative term alone on no volt row at all and on junction-current rows by at most 2.64e-11 A (a backward-Euler retry that
+# converges one sweep later: 96 kHz, a 6e-7 A base current; tests/test_oracle_sensitivity.py::test_trem_step_floors).  So volts get no
+# floor, and amps get 2.5 x that.
+ABS_FLOOR_TREM_STEP_V = 0.0
+ABS_FLOOR_TREM_STEP_I = 6.5e-11
+
 
 # Every absolute floor above with the one-ulp measurement that governs it (DESIGN.md section 2 carries the numbers).  The rule of the
 # table, asserted by tests/test_oracle_sensitivity.py on the CPU: floor <= 2.5 x (what the reference algorithm itself moves by, on the
@@ -345,6 +381,7 @@ FLOORS = {
     "ABS_FLOOR_AUDIT": ABS_FLOOR_AUDIT, "ABS_FLOOR_DENSE": ABS_FLOOR_DENSE, "ABS_FLOOR_SOAK": ABS_FLOOR_SOAK,
     "ABS_FLOOR_SOAK_LFO": ABS_FLOOR_SOAK_LFO,
     "ABS_FLOOR_MELANGE_LIT_PREAMP": ABS_FLOOR_MELANGE_LIT_PREAMP, "ABS_FLOOR_MELANGE_LIT_OUTPUT": ABS_FLOOR_MELANGE_LIT_OUTPUT,
+    "ABS_FLOOR_TREM_STEP_V": ABS_FLOOR_TREM_STEP_V, "ABS_FLOOR_TREM_STEP_I": ABS_FLOOR_TREM_STEP_I,
 }
 FLOOR_RULE = 2.5
 

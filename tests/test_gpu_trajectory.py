@@ -361,6 +361,7 @@ def test_row_oscillator_kernels_equal_the_quad_lane_kernels(hiplib, sr):
         assert np.array_equal(qa[2].view(np.uint64), ra[2].view(np.uint64)), (k, cold)
         assert np.array_equal(qa[3], ra[3]), (k, cold)
     assert worst[0] > 0, worst                                  # the kicks did hand sweeps to the generic sweep
+    assert worst[1] > 0, worst                                  # ... and did take the backward-Euler retry (the first two do in their first step: tests/trem_step_cases.py)
     print(f"\n[oscillator step at {sr:.0f} Hz] quad-lane {d[4] * 1e3 / 8192:.3f} us, row {e[4] * 1e3 / 8192:.3f} us; generic sweeps / BE retries: "
           f"{cold_settled} in 8 192 settled steps, up to {worst} in 6 000 steps after a kick")
 

@@ -330,3 +330,24 @@ def test_preamp_state_holds_the_evaluation_its_next_step_opens_with(oracle):
         if b == 30: e.reset()
         check(b)
     e.close()
+
+
+def test_trem_step_floors(oracle):
+    """ABS_FLOOR_TREM_STEP_V / _I (single steps of the Twin-T oscillator, tests/trem_step_cases.py): the oracle's own movement with pnjlim's
+    logarithm -- the step's only operation that is not IEEE arithmetic -- one double away, either way, on the rows where a floor and not the
+    relative term has to be the tolerance: the rows that move by more than 1e-5 of their value, in the finite cases that keep their exits
+    under the experiment (retry taken or not, converged or exhausted, reset; a case that changes its exit is a different step, not a
+    rounding difference, and is what the corpus counts as not comparable).  No volt row needs a floor; junction currents do."""
+    import trem_step_cases as tc
+    worst_v = worst_i = 0.0
+    for rate, ref in tc.references(oracle).items():
+        for sp, op, fp in ref.perturbed:
+            keep = ref.finite & (fp[:, [1, 3, 4]] == ref.info[:, [1, 3, 4]]).all(axis=1)
+            d = np.abs(sp[keep] - ref.states[keep])
+            d = np.where(d > 1e-5 * np.abs(ref.states[keep]), d, 0.0)
+            worst_v, worst_i = max(worst_v, float(d[:, :7].max())), max(worst_i, float(d[:, 7:].max()))
+    print(f"\n[floor table] ABS_FLOOR_TREM_STEP_V {oracle.ABS_FLOOR_TREM_STEP_V:.1e}: one-ulp-log {worst_v:.2e}; "
+          f"ABS_FLOOR_TREM_STEP_I {oracle.ABS_FLOOR_TREM_STEP_I:.1e}: one-ulp-log {worst_i:.2e} (ratio {oracle.ABS_FLOOR_TREM_STEP_I / worst_i:.2f})")
+    assert worst_v == 0.0 and 1e-12 < worst_i < 1e-10, (worst_v, worst_i)
+    assert oracle.ABS_FLOOR_TREM_STEP_V <= oracle.FLOOR_RULE * worst_v, worst_v
+    assert oracle.ABS_FLOOR_TREM_STEP_I <= oracle.FLOOR_RULE * worst_i, worst_i
