@@ -30,10 +30,11 @@ typedef struct ow_engine ow_engine;
 
 /* Version of this header's struct layouts and signatures.  ow_abi_version() returns the value the library was built with; a binding
  * checks it once after loading.  The by-pointer configuration structs (ow_batch_cfg, ow_midi_render_cfg) additionally carry their own
- * size in their first field, and ow_batch_cfg / ow_calibrate_cfg / ow_preamp_measure_cfg / ow_poly_cfg the size of one ow_job / ow_calib_point / ow_preamp_point / ow_poly_chord: a caller built
+ * size in their first field, and ow_batch_cfg / ow_calibrate_cfg / ow_preamp_measure_cfg / ow_poly_cfg / ow_centroid_cfg the size of one ow_job / ow_calib_point / ow_preamp_point / ow_poly_chord /
+ * ow_centroid_job: a caller built
  * against another header is refused ("ABI mismatch",
  * negative return) instead of having fields read past the end of what it passed. */
-#define OW_ABI_VERSION 7
+#define OW_ABI_VERSION 8
 int ow_abi_version(void);
 
 /* VoiceState, crates/openwurli-dsp/src/engine.rs:30-37 */
@@ -451,6 +452,74 @@ typedef struct ow_poly_row {
  *   - OW_POWER_AMP_MELANGE: the 7-BJT solver runs as its own launch between the preamp and the speaker stage (as in ow_batch_render). */
 long long ow_render_poly(const ow_poly_chord* chords, size_t n_chords, const ow_poly_cfg* cfg, ow_poly_row* rows_out,
                          double* final_out, double* separate_sum_out, double* residual_out, size_t stride);
+
+/* ---- centroid tracking (`preamp-bench centroid-track`, tools/preamp-bench/src/main.rs:1925-2135) ------------------------------ */
+/* One note: Voice::render_note_with_scale(note, velocity / 127, duration, 44100, displacement scale) -- MLP off, attack noise on, seed
+ * note * 2654435761 -- through a fresh legacy DkPreamp at 88 200 Hz, set_ldr_resistance(r_ldr) and THEN reset() (:1989-1991: the DC
+ * solve runs at the clamped --ldr, as in render-poly and unlike `render` / ow_batch_render), per-sample 2x oversampling, x volume^2,
+ * PowerAmp::new() at the base rate unless no_poweramp, Speaker(speaker), x POST_SPEAKER_GAIN. */
+typedef struct ow_centroid_job {
+    uint8_t note;                    /* --note, 33..96 */
+    uint8_t velocity;                /* --velocity, 0..127 (velocity / 127.0) */
+    uint8_t no_preamp;               /* --no-preamp: the reed / pickup signal goes straight to the output stage */
+    uint8_t no_poweramp;             /* --no-poweramp */
+    uint8_t has_displacement_scale;  /* --displacement-scale given */
+    uint8_t reserved[3];
+    double displacement_scale;       /* Voice::set_displacement_scale when has_displacement_scale */
+    double volume;                   /* --volume (default 0.60; applied squared) */
+    double speaker;                  /* --speaker character (default 1.0) */
+    double r_ldr;                    /* --ldr (default 1e6) */
+} ow_centroid_job;
+/* The frame grid is per call: every job of a call has the same frames.  window / hop / end in samples are (ms / 1000.0 * 44100.0) as
+ * usize (5 ms -> 220); frame j starts at j * hop and exists while pos + window <= len && pos + window / 2 <= end (integer half);
+ * its time is center_ms = (pos + window / 2.0) / 44100 * 1000 (float half).  Bins: freq_resolution = 44100 / window,
+ * k_min = ceil(50 / freq_resolution), k_max = min(floor(11025 / freq_resolution), window / 2), all in f64. */
+typedef struct ow_centroid_cfg {
+    uint32_t struct_size;  /* = sizeof(ow_centroid_cfg) of the caller's header */
+    uint32_t job_size;     /* = sizeof(ow_centroid_job) of the caller's header (the stride of `jobs`) */
+    double duration_s;     /* --duration (default 1.0) */
+    double window_ms;      /* --window-ms (default 5.0) */
+    double hop_ms;         /* --hop-ms (default 2.5) */
+    double end_ms;         /* --end-ms (default 500.0) */
+    int device;
+    int preamp_kind;       /* OW_PREAMP_LEGACY8 only (below) */
+    int power_amp_kind;    /* OW_POWER_AMP_BEHAVIORAL only (below) */
+    int reserved;
+} ow_centroid_cfg;
+#define OW_CENTROID_MAX_WINDOW 4096   /* samples (93 ms; the command's default is 5 ms): a frame then fits 32 KB of LDS */
+enum { OW_CENTROID_NO_DATA = 0, OW_CENTROID_OK = 1, OW_CENTROID_MISS = 2 };
+/* The command's summary (:2074-2129).  c10 / c300: the centroid of the FIRST frame whose center_ms >= 10.0 / >= 300.0 (frame10 /
+ * frame300, -1 and has_* = 0 when no frame reaches that far) -- even when that frame's centroid is 0.0, which then reads MISS, not
+ * "no data".  drift = c300 - c10 when both exist, else 0.  Targets by register: note <= 48, <= 72, else (:2079-2088). */
+typedef struct ow_centroid_row {
+    double c10, c300, drift;
+    double attack_lo, attack_hi, sustain_lo, sustain_hi, drift_lo, drift_hi;
+    int32_t frame10, frame300;
+    uint8_t has_c10, has_c300;
+    uint8_t attack_status, sustain_status, drift_status;   /* OW_CENTROID_OK / OW_CENTROID_MISS; OW_CENTROID_NO_DATA where the command prints no figure */
+    uint8_t reserved[3];
+} ow_centroid_row;
+/* Host only: the number of frames the command's `while` loop visits for this configuration (to size buffers); <0 when the configuration
+ * is refused (ow_last_error says why). */
+long long ow_centroid_frame_count(const ow_centroid_cfg* cfg);
+/* cmd_centroid_track for n_jobs notes at once.  frames_out: host f64 [n_jobs][frames_stride >= frames], the centroid in Hz per frame,
+ * 0.0 where the reference's `power_sum > 0.0` fails.  rows_out: [n_jobs].  audio_out: NULL, or host f64 [n_jobs][audio_stride >=
+ * (duration_s * 44100) as usize] receiving final_output; asking for it changes no number.  The audio stays in HBM for the analysis;
+ * large grids run in chunks of a fixed device-memory budget (OW_CENTROID_CHUNK=<jobs> caps a chunk; tests use it).  A job's numbers do
+ * not depend on the other jobs of the call.
+ * Returns the frame count, <0 on error.  Refused before any device work (ow_last_error says why): "ABI mismatch", a note outside 33..96,
+ * a velocity above 127, a non-finite volume, speaker or displacement_scale, a non-finite or non-positive r_ldr, a hop of 0 samples (the
+ * reference would loop forever), a window with no bin in range (k_min > k_max), a window of more than OW_CENTROID_MAX_WINDOW samples, a
+ * short stride, and, for the reasons given at ow_render_poly, OW_PREAMP_MELANGE12 (the melange adapter's reset() discards --ldr) and
+ * OW_POWER_AMP_MELANGE (the 7-BJT solver needs its own launch). */
+long long ow_centroid_track(const ow_centroid_job* jobs, size_t n_jobs, const ow_centroid_cfg* cfg, ow_centroid_row* rows_out,
+                            double* frames_out, size_t frames_stride, double* audio_out, size_t audio_stride);
+/* The analysis stage alone (spectral_centroid :1931-1958 over the periodic-Hann frames of :2021-2056) on n_rows given rows: signals f64
+ * [n_rows][stride], the first `len` samples of a row are analysed (a device pointer if signals_is_device != 0, e.g. what
+ * ow_batch_render left in HBM), at 44 100 Hz.  frames_out: host f64 [n_rows][frames_stride >= frames]; entries past the frame count are
+ * left untouched.  Returns the frame count (0: nothing written), <0 on error; the same refusals for hop, window and strides. */
+long long ow_centroid_analyze(const double* signals, size_t n_rows, size_t stride, size_t len, size_t window_samples, size_t hop_samples,
+                              size_t end_sample, int device, int signals_is_device, double* frames_out, size_t frames_stride);
 
 #ifdef __cplusplus
 }

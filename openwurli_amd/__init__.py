@@ -14,5 +14,6 @@ from . import midi_render  # noqa: F401
 from . import calibrate  # noqa: F401
 from . import preamp_bench  # noqa: F401
 from . import render_poly  # noqa: F401
+from . import centroid_track  # noqa: F401
 
-__all__ = ["load_library", "library_path", "OwError", "WurliEngine", "EnginePool", "VoiceState", "render_note", "batch_render", "normalize_scale", "tremolo_prefetch", "tremolo_configure", "tremolo_export", "tremolo_import", "features", "alias_audit", "midi_render", "calibrate", "preamp_bench", "render_poly"]
+__all__ = ["load_library", "library_path", "OwError", "WurliEngine", "EnginePool", "VoiceState", "render_note", "batch_render", "normalize_scale", "tremolo_prefetch", "tremolo_configure", "tremolo_export", "tremolo_import", "features", "alias_audit", "midi_render", "calibrate", "preamp_bench", "render_poly", "centroid_track"]

@@ -38,7 +38,7 @@ class OwMidiEvent(C.Structure):
 MIDI_DTYPE = [("engine", "<u4"), ("type", "u1"), ("note", "u1"), ("reserved", "<u2"), ("value", "<f4")]
 
 
-ABI_VERSION = 7      # include/openwurli_hip.h OW_ABI_VERSION; load_library() checks it against ow_abi_version()
+ABI_VERSION = 8      # include/openwurli_hip.h OW_ABI_VERSION; load_library() checks it against ow_abi_version()
 
 
 class OwBatchCfg(C.Structure):
@@ -145,6 +145,32 @@ class OwPolyRow(C.Structure):
                 ("peak_db", C.c_double * 3), ("rms_db", C.c_double * 3), ("intermod_ratio_db", C.c_double)]
 
 
+CENTROID_MAX_WINDOW = 4096                                  # include/openwurli_hip.h OW_CENTROID_MAX_WINDOW
+CENTROID_NO_DATA, CENTROID_OK, CENTROID_MISS = 0, 1, 2      # the status bytes of ow_centroid_row
+
+
+class OwCentroidJob(C.Structure):
+    _fields_ = [("note", C.c_uint8), ("velocity", C.c_uint8), ("no_preamp", C.c_uint8), ("no_poweramp", C.c_uint8),
+                ("has_displacement_scale", C.c_uint8), ("reserved", C.c_uint8 * 3), ("displacement_scale", C.c_double),
+                ("volume", C.c_double), ("speaker", C.c_double), ("r_ldr", C.c_double)]
+
+
+class OwCentroidCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("job_size", C.c_uint32), ("duration_s", C.c_double), ("window_ms", C.c_double),
+                ("hop_ms", C.c_double), ("end_ms", C.c_double), ("device", C.c_int), ("preamp_kind", C.c_int), ("power_amp_kind", C.c_int),
+                ("reserved", C.c_int)]
+
+    def __init__(self, duration_s=1.0, window_ms=5.0, hop_ms=2.5, end_ms=500.0, device=0, preamp_kind=0, power_amp_kind=0):
+        super().__init__(C.sizeof(OwCentroidCfg), C.sizeof(OwCentroidJob), duration_s, window_ms, hop_ms, end_ms, device, preamp_kind, power_amp_kind, 0)
+
+
+class OwCentroidRow(C.Structure):
+    _fields_ = [("c10", C.c_double), ("c300", C.c_double), ("drift", C.c_double), ("attack_lo", C.c_double), ("attack_hi", C.c_double),
+                ("sustain_lo", C.c_double), ("sustain_hi", C.c_double), ("drift_lo", C.c_double), ("drift_hi", C.c_double),
+                ("frame10", C.c_int32), ("frame300", C.c_int32), ("has_c10", C.c_uint8), ("has_c300", C.c_uint8),
+                ("attack_status", C.c_uint8), ("sustain_status", C.c_uint8), ("drift_status", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
 # every symbol include/openwurli_hip.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 class OwSegment(C.Structure):
@@ -227,6 +253,9 @@ SYMBOLS = {
     "ow_calibrate": (C.c_int, [_VP, C.c_size_t, C.POINTER(OwCalibrateCfg), _VP, _VP, C.c_size_t]),
     "ow_preamp_measure": (C.c_int, [_VP, C.c_size_t, C.POINTER(OwPreampMeasureCfg), _VP, _VP, C.c_size_t]),
     "ow_render_poly": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwPolyCfg), _VP, _VP, _VP, _VP, C.c_size_t]),
+    "ow_centroid_frame_count": (C.c_longlong, [C.POINTER(OwCentroidCfg)]),
+    "ow_centroid_track": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwCentroidCfg), _VP, _VP, C.c_size_t, _VP, C.c_size_t]),
+    "ow_centroid_analyze": (C.c_longlong, [_VP, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _VP, C.c_size_t]),
 }
 
 

@@ -72,7 +72,7 @@ long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg*
         for (size_t i = 0; i < n_jobs; ++i) {
             hj[i].note = jobs[i].note; hj[i].velocity = jobs[i].velocity; hj[i].mlp = jobs[i].mlp; hj[i].poweramp = jobs[i].poweramp;
             hj[i].no_preamp = jobs[i].no_preamp ? 1 : 0; hj[i].no_attack_noise = jobs[i].no_attack_noise ? 1 : 0;
-            hj[i].has_ds = jobs[i].has_displacement_scale ? 1 : 0; hj[i].pad8 = 0;
+            hj[i].has_ds = jobs[i].has_displacement_scale ? 1 : 0; hj[i].dc_at_ldr = 0;
             hj[i].volume = jobs[i].volume; hj[i].speaker = jobs[i].speaker; hj[i].r_ldr = jobs[i].r_ldr;
             hj[i].tremolo_depth = jobs[i].tremolo_depth; hj[i].displacement_scale = jobs[i].displacement_scale;
         }

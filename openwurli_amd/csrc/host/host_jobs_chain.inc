@@ -63,7 +63,7 @@ static bool job_chain_is_plain_legacy(const JobChainCfg& cfg, const std::vector<
     if (cfg.preamp_kind != OW_PREAMP_LEGACY8) return false;
     bool any_pa = false;
     for (const auto& j : hj) {
-        if ((j.tremolo_depth > 0.0 && !j.no_preamp) || j.no_preamp) return false;
+        if ((j.tremolo_depth > 0.0 && !j.no_preamp) || j.no_preamp || j.dc_at_ldr) return false;
         any_pa = any_pa || j.poweramp;
     }
     return !(cfg.power_amp_kind == OW_POWER_AMP_MELANGE && any_pa);
@@ -75,7 +75,7 @@ void run_job_chain(const JobChainCfg& cfg, const OwConsts* dK, const std::vector
     bool any_trem = false, any_special = false, any_pa = false;
     for (const auto& j : hj) {
         any_trem = any_trem || (j.tremolo_depth > 0.0 && !j.no_preamp);
-        any_special = any_special || j.no_preamp;
+        any_special = any_special || j.no_preamp || j.dc_at_ldr;      // dc_at_ldr (centroid-track): only k_job_chain knows it
         any_pa = any_pa || j.poweramp;
     }
     const bool mpa = cfg.power_amp_kind == OW_POWER_AMP_MELANGE && any_pa;

@@ -37,6 +37,7 @@
 #include "ow_calib_kernels.h"
 #include "ow_pbench_kernels.h"
 #include "ow_poly_kernels.h"
+#include "ow_centroid_kernels.h"
 #include "ow_midi_kernels.h"
 #include "ow_chain_wide.h"
 #include "ow_chain_stream.h"
@@ -65,3 +66,4 @@ using owdev::OwEngineOut;
 #include "host/api_calibrate.inc"       // C-ABI: `preamp-bench calibrate` / `sensitivity` (the calibration sweep)
 #include "host/api_preamp_measure.inc"  // C-ABI: `preamp-bench gain` / `sweep` / `harmonics` / `tremolo-sweep` (the preamp measurements)
 #include "host/api_render_poly.inc"     // C-ABI: `preamp-bench render-poly` (chord intermodulation, many chords per call)
+#include "host/api_centroid.inc"        // C-ABI: `preamp-bench centroid-track` (spectral centroid over time, many notes per call)

@@ -15,7 +15,8 @@ namespace owdev {
 
 struct OwJobDev {           // device copy of ow_job
     uint8_t note, velocity, mlp, poweramp;
-    uint8_t no_preamp, no_attack_noise, has_ds, pad8;
+    uint8_t no_preamp, no_attack_noise, has_ds;
+    uint8_t dc_at_ldr;           // device-internal (no ow_job field; 0 for `render`): set_ldr_resistance(r_ldr) BEFORE reset(), as `centroid-track` does (main.rs:1989-1991)
     double volume, speaker, r_ldr;
     double tremolo_depth;        // > 0: Tremolo::new(depth, preamp_sr) drives the LDR (main.rs:430-431), the static --ldr is ignored
     double displacement_scale;   // has_ds: Voice::set_displacement_scale (main.rs:406-408)
@@ -112,7 +113,11 @@ __global__ __launch_bounds__(64) void k_job_chain(const OwConsts* __restrict__ K
         ms.nan_resets = 0; ms.be_fallbacks = 0;
         if (!use_trem) mel_set_r(ms, jd.r_ldr);
     } else {
-        dk_dc_reset(K, r_ldr, st);                   // new() and reset() both solve DC at the initial 1 Mohm
+        if (jd.dc_at_ldr && !use_trem) {             // set_ldr_resistance(r) and THEN reset(): the DC solve runs at the clamped --ldr, and
+            const double r_new = fmax(jd.r_ldr, 1000.0);   // reset() leaves g_ldr_prev = g_ldr (dk_preamp_legacy.rs:620-640)
+            if (fabs(r_new - r_ldr) > 0.01) { r_ldr = r_new; g_ldr = 1.0 / r_new; g_prev = g_ldr; }
+        }
+        dk_dc_reset(K, r_ldr, st);                   // else: new() and reset() both solve DC at the initial 1 Mohm
         if (!use_trem) {
             const double r_new = fmax(jd.r_ldr, 1000.0);
             if (fabs(r_new - r_ldr) > 0.01) { r_ldr = r_new; g_ldr = 1.0 / r_new; }
