@@ -1,0 +1,33 @@
+"""What the preamp-bench command modules share: the reference's base rate, Rust's number conversions and number formatting."""
+import math
+
+BASE_SR = 44100.0                                           # main.rs:27
+
+
+def midi_note_name(note: int) -> str:
+    """main.rs:666-673."""
+    return "%s%d" % (("C", "C#", "D", "D#", "E", "F", "F#", "G", "G#", "A", "A#", "B")[note % 12], note // 12 - 1)
+
+
+def as_usize(x: float) -> int:
+    """Rust's `f64 as usize`: NaN and negatives give 0."""
+    return int(x) if x > 0 and math.isfinite(x) else 0
+
+
+def samples(duration: float) -> int:
+    """(duration * BASE_SR) as usize."""
+    return as_usize(float(duration) * BASE_SR)
+
+
+def to_dbfs(val: float) -> float:
+    """main.rs:2241-2247."""
+    return 20.0 * math.log10(val) if val > 1e-15 else -120.0
+
+
+def _f(x, spec):
+    """Rust's {:spec}: it rounds the exact binary value half to even, as Python's %-format does, but prints NaN as "NaN" (padded to the
+    width, without a sign) where Python prints "nan"; inf is "inf" in both."""
+    x = float(x)
+    if math.isnan(x):
+        return ("%" + spec.split(".")[0].lstrip("+") + "s") % "NaN"
+    return ("%" + spec) % x

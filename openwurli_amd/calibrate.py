@@ -12,7 +12,7 @@ import numpy as np
 from .binding import (CALIB_SAMPLES, CALIBRATE_ROW_FIELDS, OwCalibPoint, OwCalibrateCfg, OwCalibrateRow, OwError, load_library,
                       take_error)
 
-BASE_SR = 44100.0                                           # main.rs:27
+from ._rust_text import BASE_SR, midi_note_name  # noqa: F401
 MIDI_LO, MIDI_HI = 33, 96                                   # tables.rs:6-7
 PREAMP_LEGACY8, PREAMP_MELANGE12 = 0, 1
 POWER_AMP_BEHAVIORAL, POWER_AMP_MELANGE = 0, 1
@@ -66,11 +66,6 @@ POINT_DTYPE = np.dtype([("note", "u1"), ("velocity", "u1"), ("zero_trim", "u1"),
                         ("target_db", "<f8"), ("voicing_slope", "<f8")])
 ROW_DTYPE = np.dtype([("midi", "u1"), ("velocity", "u1"), ("reserved", "u1", (6,))] + [(f, "<f8") for f in CALIBRATE_ROW_FIELDS])
 assert POINT_DTYPE.itemsize == C.sizeof(OwCalibPoint) and ROW_DTYPE.itemsize == C.sizeof(OwCalibrateRow)
-
-
-def midi_note_name(note: int) -> str:                      # main.rs:666-673
-    names = ("C", "C#", "D", "D#", "E", "F", "F#", "G", "G#", "A", "A#", "B")
-    return f"{names[note % 12]}{note // 12 - 1}"
 
 
 def make_points(notes: Sequence[int], velocities: Sequence[int], cfgs: Sequence[CalibrationConfig]) -> np.ndarray:

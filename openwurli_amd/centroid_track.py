@@ -16,9 +16,8 @@ import numpy as np
 
 from .binding import (CENTROID_MAX_WINDOW, CENTROID_MISS, CENTROID_NO_DATA, CENTROID_OK, OwCentroidCfg, OwCentroidJob, OwCentroidRow, OwError,
                       load_library, take_error)
-from .render_poly import _f, midi_note_name
+from ._rust_text import BASE_SR, _f, as_usize as _as_usize, midi_note_name, samples  # noqa: F401
 
-BASE_SR = 44100.0                                           # main.rs:27
 ML_VELOCITIES = (20, 35, 50, 65, 80, 95, 110, 127)          # the ML pipeline's velocity layers (ml/render_model_notes.py:26)
 STATUS = {CENTROID_NO_DATA: "", CENTROID_OK: "OK", CENTROID_MISS: "MISS"}
 
@@ -51,19 +50,9 @@ def make_jobs(jobs) -> np.ndarray:
     return np.concatenate(out) if out else np.zeros(0, dtype=JOB_DTYPE)
 
 
-def _as_usize(x: float) -> int:
-    """Rust's `f64 as usize`: NaN and negatives give 0."""
-    return int(x) if x > 0 and math.isfinite(x) else 0
-
-
 def ms_to_samples(ms: float) -> int:
     """((ms / 1000.0) * BASE_SR) as usize (main.rs:2012-2014): 5 ms -> 220."""
     return _as_usize((float(ms) / 1000.0) * BASE_SR)
-
-
-def samples(duration: float) -> int:
-    """(duration * BASE_SR) as usize."""
-    return _as_usize(float(duration) * BASE_SR)
 
 
 def bin_range(window_samples: int):

@@ -83,27 +83,10 @@ inline double output_scale(int midi, double velocity_norm, const ow_calib_point&
     const double effective_trim = trim * vel_blend;
     return std::pow(10.0, (c.target_db + flat_db + voicing_db + effective_trim) / 20.0);
 }
-// main.rs:912-937, 2241-2247 (the sums come from k_calib_metrics)
-inline double to_dbfs(double val) { return val > 1e-15 ? 20.0 * std::log10(val) : -120.0; }
-inline double rms_db(double sumsq, double n) {
-    const double mean_sq = sumsq / n;
-    return mean_sq > 0.0 ? 10.0 * std::log10(mean_sq) : -120.0;
-}
-inline double dft_magnitude(double re, double im, double n) {                                            // main.rs:893-903
-    const double a = re / n, b = im / n;
-    return 2.0 * std::sqrt(a * a + b * b);
-}
-inline double h2_h1_ratio_db(const double* m, double n) {                                                // main.rs:929-937
-    const double h1 = dft_magnitude(m[owdev::CALIB_MET_RE1], m[owdev::CALIB_MET_IM1], n);
-    const double h2 = dft_magnitude(m[owdev::CALIB_MET_RE2], m[owdev::CALIB_MET_IM2], n);
+inline double h2_h1_ratio_db(const double* m, double n) {                                                // main.rs:929-937 (the sums come from k_calib_metrics)
+    const double h1 = measure::dft_magnitude(m[owdev::CALIB_MET_RE1], m[owdev::CALIB_MET_IM1], n);
+    const double h2 = measure::dft_magnitude(m[owdev::CALIB_MET_RE2], m[owdev::CALIB_MET_IM2], n);
     return h1 > 1e-15 ? 20.0 * std::log10(h2 / h1) : -120.0;
-}
-// points per chunk: a fixed device budget of ~8 GiB at four (five with taps) rows of 0.5 s per point, capped by `cap` (> 0; the
-// OW_CALIB_CHUNK switch, tests)
-inline size_t chunk_points(size_t row_bytes, int rows, long long cap) {
-    size_t c = (size_t(8) << 30) / (row_bytes * (size_t)rows);
-    if (cap > 0) c = std::min(c, (size_t)cap);
-    return std::max<size_t>(c, 1);
 }
 }  // namespace calib
 }  // namespace
@@ -114,12 +97,10 @@ int ow_calibrate(const ow_calib_point* points, size_t n_pts, const ow_calibrate_
     try {
         if (!cfg) throw std::runtime_error("null argument");
         if (cfg->struct_size != sizeof(ow_calibrate_cfg) || cfg->point_size != sizeof(ow_calib_point))
-            throw std::runtime_error("ABI mismatch: ow_calibrate_cfg.struct_size / point_size do not match this library's openwurli_hip.h (OW_ABI_VERSION " +
-                                     std::to_string(OW_ABI_VERSION) + ")");
+            throw std::runtime_error(abi_mismatch("ow_calibrate_cfg.struct_size / point_size do"));
         if (n_pts == 0) return 0;
         if (!points || !rows_out) throw std::runtime_error("null argument");
-        if (cfg->preamp_kind != OW_PREAMP_LEGACY8 && cfg->preamp_kind != OW_PREAMP_MELANGE12) throw std::runtime_error("unknown preamp_kind");
-        if (cfg->power_amp_kind != OW_POWER_AMP_BEHAVIORAL && cfg->power_amp_kind != OW_POWER_AMP_MELANGE) throw std::runtime_error("unknown power_amp_kind");
+        require_known_kinds(cfg->preamp_kind, cfg->power_amp_kind);
         const long long n = OW_CALIB_SAMPLES;                          // (0.5 * BASE_SR) as usize, main.rs:1136,1172
         if (taps_out && taps_stride < (size_t)n) throw std::runtime_error("taps_stride smaller than " + std::to_string(n));
         if (n_pts > (size_t)INT32_MAX) throw std::runtime_error("too many points");
@@ -127,49 +108,36 @@ int ow_calibrate(const ow_calib_point* points, size_t n_pts, const ow_calibrate_
         std::vector<owdev::OwCalibDev> hp(n_pts);
         for (size_t i = 0; i < n_pts; ++i) {
             const ow_calib_point& c = points[i];
-            if (c.note < OW_MIDI_LO || c.note > OW_MIDI_HI)
-                throw std::runtime_error("point " + std::to_string(i) + ": note " + std::to_string(c.note) + " outside 33..96 (the tables' range)");
-            if (c.velocity > 127)
-                throw std::runtime_error("point " + std::to_string(i) + ": velocity " + std::to_string(c.velocity) + " above 127 (a MIDI velocity byte)");
-            if (!(c.ds_clamp_lo <= c.ds_clamp_hi)) throw std::runtime_error("point " + std::to_string(i) + ": ds_clamp lo > hi or NaN (f64::clamp panics)");
+            const std::string at = "point " + std::to_string(i) + ": ";
+            check_note_velocity(at, c.note, c.velocity);
+            if (!(c.ds_clamp_lo <= c.ds_clamp_hi)) throw std::runtime_error(at + "ds_clamp lo > hi or NaN (f64::clamp panics)");
             hp[i].note = c.note; hp[i].velocity = c.velocity;
             hp[i].ds_actual = calib::pickup_displacement_scale(c.note, c);
             hp[i].out_scale = calib::output_scale(c.note, (double)c.velocity / 127.0, c);
             hp[i].f0 = calib::midi_to_freq(c.note);
         }
-        int ndev = 0;
-        HIP_OK(hipGetDeviceCount(&ndev));
-        if (ndev <= 0) throw std::runtime_error("no HIP device: openwurli-hip has no CPU fallback");
-        HIP_OK(hipSetDevice(cfg->device));
-        std::unique_ptr<OwConsts> hc(new OwConsts());
-        owhip::build_consts(*hc, sr, cfg->preamp_kind);
+        OfflineCall call(cfg->device, sr, cfg->preamp_kind, /*note_table=*/true);
+        hipStream_t st = call.st();
+        const OwConsts* dK = call.dK();
         const bool mel = cfg->preamp_kind == OW_PREAMP_MELANGE12, mpa = cfg->power_amp_kind == OW_POWER_AMP_MELANGE;
-        const long long stride = (n + 63) / 64 * 64;                  // 512-byte aligned rows
+        const long long stride = row_stride(n);
         const size_t row_bytes = sizeof(double) * (size_t)stride;
         const int n_rows = taps_out ? 5 : 4;
-        const Switches sw = Switches::from_env();          // offline entry point: read once per call
-        const size_t chunk = std::min(n_pts, calib::chunk_points(row_bytes, n_rows, sw.calib_chunk));
-        StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
-        hipStream_t st = so.s;
-        DevMem m_K, m_nt, m_vrec, m_pts, m_jobs, m_rows, m_pk, m_met, m_settled, m_pac, m_pas;   // released on every exit path
-        m_K.alloc(sizeof(OwConsts));
-        m_nt.alloc(sizeof(double) * NT_COUNT * 64);
+        // points per chunk: ~8 GiB of device rows at four (five with taps) rows of 0.5 s per point
+        const size_t chunk = budget_chunk(size_t(8) << 30, row_bytes * (size_t)n_rows, call.sw.calib_chunk, n_pts);
+        DevMem m_vrec, m_pts, m_jobs, m_rows, m_pk, m_met;            // released on every exit path
         m_vrec.alloc(sizeof(double) * ((chunk + 63) / 64) * OW_VREC_DOUBLES);
         m_pts.alloc(sizeof(owdev::OwCalibDev) * n_pts);
         m_jobs.alloc(sizeof(owdev::OwJobDev) * chunk);
         m_rows.alloc(row_bytes * chunk * (size_t)n_rows);
         m_pk.alloc(sizeof(double) * n_pts);
         m_met.alloc(sizeof(double) * n_pts * 4 * owdev::CALIB_MET_COUNT);
-        OwConsts* dK = m_K.as<OwConsts>();
         owdev::OwCalibDev* d_pts = m_pts.as<owdev::OwCalibDev>();
         double* rows = m_rows.as<double>();
         double* T[5];                                                  // T1..T5 row blocks of a chunk ([chunk][stride] each)
         T[1] = rows; T[2] = rows + (size_t)chunk * stride; T[3] = rows + 2 * (size_t)chunk * stride; T[4] = rows + 3 * (size_t)chunk * stride;
         T[0] = taps_out ? rows + 4 * (size_t)chunk * stride : nullptr;
-        HIP_OK(hipMemcpyAsync(dK, hc.get(), sizeof(OwConsts), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_pts, hp.data(), sizeof(owdev::OwCalibDev) * n_pts, hipMemcpyHostToDevice, st));
-        owdev::k_note_table<<<dim3(1), dim3(64), 0, st>>>(m_nt.as<double>());
         // T4's jobs: `preamp-bench render`'s chain with a static 1 Mohm LDR and volume 1.0, stopped at the power amp's input
         // (JOB_OUT_PA_INPUT: pre x 1.0 x 1.0 = pre, bit for bit).  run_calibrate builds its preamp with new() + set_ldr_resistance(1e6) and no
         // reset() (main.rs:1190-1191), the batch job with new() + reset() + set_ldr_resistance: the same start state for both kinds --
@@ -182,31 +150,19 @@ int ow_calibrate(const ow_calib_point* points, size_t n_pts, const ow_calibrate_
             j.poweramp = 1; j.volume = 1.0; j.speaker = cfg->speaker; j.r_ldr = 1000000.0;
         }
         HIP_OK(hipMemcpyAsync(m_jobs.p, hj.data(), sizeof(owdev::OwJobDev) * chunk, hipMemcpyHostToDevice, st));
-        if (mel) {
-            m_settled.alloc(sizeof(double) * 18);
-            mel_settled_to_device(cfg->device, m_settled.as<double>(), st);
-        }
-        std::unique_ptr<OwPaConsts> hpa;
-        if (mpa) {                                                     // PowerAmp::new() = new_at_sample_rate(44 100), rail sag on (power_amp.rs:321-323)
-            hpa.reset(new OwPaConsts());
-            owhip::build_pa_consts(*hpa, 44100.0);
-            m_pac.alloc(sizeof(OwPaConsts));
-            m_pas.alloc(sizeof(double) * owdev::PAS_CIRCUIT_END);
-            pa_settled_to_device(cfg->device, m_pas.as<double>(), st);
-            HIP_OK(hipMemcpyAsync(m_pac.p, hpa.get(), sizeof(OwPaConsts), hipMemcpyHostToDevice, st));
-        }
+        const double* settled = mel ? call.mel_settled() : nullptr;
+        std::unique_ptr<MelPowerAmpStage> pa;
+        if (mpa) pa.reset(new MelPowerAmpStage(cfg->device, st));
         const double nwin = (double)(OW_CALIB_WIN_HI - OW_CALIB_WIN_LO);
-        const size_t tap_pitch = 5 * taps_stride * sizeof(double);
         auto copy_taps = [&](int k, size_t p0, size_t cn) {           // T(k+1) rows of the chunk -> taps_out[p][k][0..n)
-            HIP_OK(hipMemcpy2DAsync(taps_out + (p0 * 5 + (size_t)k) * taps_stride, tap_pitch, T[k], row_bytes, sizeof(double) * (size_t)n, cn,
-                                    hipMemcpyDeviceToHost, st));
+            rows_to_host(taps_out + (p0 * 5 + (size_t)k) * taps_stride, 5 * taps_stride, T[k], (size_t)stride, (size_t)n, cn, st);
         };
         for (size_t p0 = 0; p0 < n_pts; p0 += chunk) {
             const size_t cn = std::min(chunk, n_pts - p0);
             const int ci = (int)cn;
             const owdev::OwCalibDev* cp = d_pts + p0;
             double* met = m_met.as<double>() + p0 * 4 * owdev::CALIB_MET_COUNT;
-            owdev::k_calib_voice<<<dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, st>>>(dK, m_nt.as<double>(), m_vrec.as<double>(), cp, T[0], T[1], T[2],
+            owdev::k_calib_voice<<<dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, st>>>(dK, call.nt(), m_vrec.as<double>(), cp, T[0], T[1], T[2],
                                                                                          m_pk.as<double>() + p0, ci, n, stride);
             HIP_OK(hipGetLastError());
             if (taps_out) { copy_taps(0, p0, cn); copy_taps(1, p0, cn); copy_taps(2, p0, cn); }
@@ -215,17 +171,16 @@ int ow_calibrate(const ow_calib_point* points, size_t n_pts, const ow_calibrate_
             owdev::k_calib_metrics<<<dim3((unsigned)cn, 2), dim3(256), 0, st>>>(a23, cp, stride, sr, 1u, 0, met);
             HIP_OK(hipGetLastError());
             if (mel)
-                owdev::k_job_chain<true><<<dim3((unsigned)((cn + 31) / 32)), dim3(64), 0, st>>>(dK, m_jobs.as<owdev::OwJobDev>(), T[2], T[3], m_settled.as<double>(),
+                owdev::k_job_chain<true><<<dim3((unsigned)((cn + 31) / 32)), dim3(64), 0, st>>>(dK, m_jobs.as<owdev::OwJobDev>(), T[2], T[3], settled,
                                                                                                 ci, n, stride, nullptr, owdev::JOB_OUT_PA_INPUT);
             else
                 owdev::k_job_chain<false><<<dim3((unsigned)((cn + 31) / 32)), dim3(64), 0, st>>>(dK, m_jobs.as<owdev::OwJobDev>(), T[2], T[3], nullptr,
                                                                                                  ci, n, stride, nullptr, owdev::JOB_OUT_PA_INPUT);
             HIP_OK(hipGetLastError());
             const unsigned ob = (unsigned)((cn + 63) / 64);
-            if (mpa) {        // as run_job_chain: t4 x volume^2 -> the 7-BJT solver at 44.1 kHz (eight lanes per point) -> speaker
+            if (mpa) {        // as run_job_chain: t4 x volume^2 -> the melange power amp, rail sag on -> speaker
                 owdev::k_calib_out<<<dim3(ob), dim3(64), 0, st>>>(dK, T[3], T[1], cfg->volume, cfg->speaker, ci, n, stride, owdev::CALIB_OUT_ATT);
-                owdev::k_mpa_debug<<<dim3((unsigned)((cn + PA_EPB - 1) / PA_EPB)), dim3(PA_WPB * 64), 0, st>>>(m_pac.as<OwPaConsts>(), m_pas.as<double>(), T[1], T[2],
-                                                                                                              nullptr, n, ci, 1, nullptr, nullptr, nullptr, stride);
+                pa->run(T[1], T[2], n, ci, 1, stride);
                 owdev::k_calib_out<<<dim3(ob), dim3(64), 0, st>>>(dK, T[2], T[4], cfg->volume, cfg->speaker, ci, n, stride, owdev::CALIB_OUT_SPEAKER);
             } else {
                 owdev::k_calib_out<<<dim3(ob), dim3(64), 0, st>>>(dK, T[3], T[4], cfg->volume, cfg->speaker, ci, n, stride, owdev::CALIB_OUT_FULL);
@@ -250,12 +205,12 @@ int ow_calibrate(const ow_calib_point* points, size_t n_pts, const ow_calibrate_
             std::memset(&r, 0, sizeof(r));
             r.midi = c.note; r.velocity = c.velocity;
             r.ds_at_c4 = c.ds_at_c4; r.ds_actual = hp[i].ds_actual; r.y_peak = pk[i] * hp[i].ds_actual;       // main.rs:1175-1176
-            r.t2_peak_db = calib::to_dbfs(m2[owdev::CALIB_MET_PEAK]); r.t2_rms_db = calib::rms_db(m2[owdev::CALIB_MET_SUMSQ], nwin);
+            r.t2_peak_db = measure::to_dbfs(m2[owdev::CALIB_MET_PEAK]); r.t2_rms_db = measure::rms_db(m2[owdev::CALIB_MET_SUMSQ] / nwin);
             r.t2_h2_h1_db = calib::h2_h1_ratio_db(m2, nwin);
-            r.t3_peak_db = calib::to_dbfs(m3[owdev::CALIB_MET_PEAK]); r.t3_rms_db = calib::rms_db(m3[owdev::CALIB_MET_SUMSQ], nwin);
-            r.t4_peak_db = calib::to_dbfs(m4[owdev::CALIB_MET_PEAK]); r.t4_rms_db = calib::rms_db(m4[owdev::CALIB_MET_SUMSQ], nwin);
+            r.t3_peak_db = measure::to_dbfs(m3[owdev::CALIB_MET_PEAK]); r.t3_rms_db = measure::rms_db(m3[owdev::CALIB_MET_SUMSQ] / nwin);
+            r.t4_peak_db = measure::to_dbfs(m4[owdev::CALIB_MET_PEAK]); r.t4_rms_db = measure::rms_db(m4[owdev::CALIB_MET_SUMSQ] / nwin);
             r.t4_h2_h1_db = calib::h2_h1_ratio_db(m4, nwin);
-            r.t5_peak_db = calib::to_dbfs(m5[owdev::CALIB_MET_PEAK]); r.t5_rms_db = calib::rms_db(m5[owdev::CALIB_MET_SUMSQ], nwin);
+            r.t5_peak_db = measure::to_dbfs(m5[owdev::CALIB_MET_PEAK]); r.t5_rms_db = measure::rms_db(m5[owdev::CALIB_MET_SUMSQ] / nwin);
             r.t5_h2_h1_db = calib::h2_h1_ratio_db(m5, nwin);
             r.proxy_db = 20.0 * std::log10(hp[i].out_scale);                                                   // main.rs:1225-1232
             r.trim_db = c.zero_trim ? 0.0 : calib::register_trim_db(c.note);

@@ -4,9 +4,7 @@ namespace {
 namespace centroid {
 const double SR = 44100.0;                         // BASE_SR, main.rs:27
 const size_t BUDGET_BYTES = size_t(8) << 30;       // per chunk (a job takes a voice row and an output row), as the calibration sweep's
-// Rust's `f64 as usize`: NaN and negatives give 0, large values saturate
-inline size_t as_usize(double x) { return !(x > 0.0) ? 0 : (x >= 18446744073709551615.0 ? SIZE_MAX : (size_t)x); }
-inline size_t ms_to_samples(double ms) { return as_usize((ms / 1000.0) * SR); }        // main.rs:2012-2014
+inline size_t ms_to_samples(double ms) { return rust_as_usize((ms / 1000.0) * SR); }        // main.rs:2012-2014
 
 // which frames and bins exist (main.rs:1933-1935, 2046); throws what the entry points refuse
 owdev::OwCentroidGrid make_grid(size_t len, size_t window, size_t hop, size_t end) {
@@ -16,8 +14,8 @@ owdev::OwCentroidGrid make_grid(size_t len, size_t window, size_t hop, size_t en
         throw std::runtime_error("window of " + std::to_string(window) + " samples: more than OW_CENTROID_MAX_WINDOW = " + std::to_string(OW_CENTROID_MAX_WINDOW));
     if (hop > 0xffffffffull) throw std::runtime_error("hop_samples out of range");
     const double freq_resolution = SR / (double)window;
-    const size_t k_min = as_usize(std::ceil(50.0 / freq_resolution));
-    const size_t k_max = std::min(as_usize(std::floor((SR / 4.0) / freq_resolution)), window / 2);
+    const size_t k_min = rust_as_usize(std::ceil(50.0 / freq_resolution));
+    const size_t k_max = std::min(rust_as_usize(std::floor((SR / 4.0) / freq_resolution)), window / 2);
     if (k_min > k_max)
         throw std::runtime_error("window of " + std::to_string(window) + " samples has no bin in range (k_min " + std::to_string(k_min) + " > k_max " +
                                  std::to_string(k_max) + ")");
@@ -85,17 +83,11 @@ void summarise(uint8_t note, const double* c, const owdev::OwCentroidGrid& g, ow
 owdev::OwCentroidGrid checked_grid(const ow_centroid_cfg* cfg, size_t* n_out) {
     if (!cfg) throw std::runtime_error("null argument");
     if (cfg->struct_size != sizeof(ow_centroid_cfg) || cfg->job_size != sizeof(ow_centroid_job))
-        throw std::runtime_error("ABI mismatch: ow_centroid_cfg.struct_size / job_size do not match this library's openwurli_hip.h (OW_ABI_VERSION " +
-                                 std::to_string(OW_ABI_VERSION) + ")");
-    if (cfg->preamp_kind == OW_PREAMP_MELANGE12)
-        throw std::runtime_error("preamp_kind OW_PREAMP_MELANGE12 is not supported: the melange preamp's reset() discards --ldr (see openwurli_hip.h)");
-    if (cfg->preamp_kind != OW_PREAMP_LEGACY8) throw std::runtime_error("unknown preamp_kind");
-    if (cfg->power_amp_kind == OW_POWER_AMP_MELANGE)
-        throw std::runtime_error("power_amp_kind OW_POWER_AMP_MELANGE is not supported: it needs its own launch between the stages (see openwurli_hip.h)");
-    if (cfg->power_amp_kind != OW_POWER_AMP_BEHAVIORAL) throw std::runtime_error("unknown power_amp_kind");
+        throw std::runtime_error(abi_mismatch("ow_centroid_cfg.struct_size / job_size do"));
+    require_legacy_chain(cfg->preamp_kind, cfg->power_amp_kind);
     const double x = cfg->duration_s * SR;               // Voice::render_note_with_scale: (duration * sample_rate) as usize
     if (!(x < 2147483648.0)) throw std::runtime_error("duration_s must give fewer than 2^31 samples");
-    const size_t n = as_usize(x);
+    const size_t n = rust_as_usize(x);
     *n_out = n;
     return make_grid(n, ms_to_samples(cfg->window_ms), ms_to_samples(cfg->hop_ms), ms_to_samples(cfg->end_ms));
 }
@@ -118,10 +110,7 @@ long long ow_centroid_analyze(const double* signals, size_t n_rows, size_t strid
         if (g.frames == 0 || n_rows == 0) return g.frames;
         if (!signals || !frames_out) throw std::runtime_error("null argument");
         if (frames_stride < g.frames) throw std::runtime_error("frames_stride smaller than the " + std::to_string(g.frames) + " frames of a row");
-        int ndev = 0;
-        HIP_OK(hipGetDeviceCount(&ndev));
-        if (ndev <= 0) throw std::runtime_error("no HIP device: openwurli-hip has no CPU fallback");
-        HIP_OK(hipSetDevice(device));
+        require_device(device);
         StreamOwner so;
         HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
         DevMem d_sig, d_hann, d_frames;
@@ -136,8 +125,7 @@ long long ow_centroid_analyze(const double* signals, size_t n_rows, size_t strid
         d_frames.alloc(sizeof(double) * n_rows * g.frames);
         HIP_OK(hipMemcpyAsync(d_hann.p, hann.data(), sizeof(double) * hann.size(), hipMemcpyHostToDevice, so.s));
         centroid::launch_frames(src, n_rows, stride, d_hann.as<double>(), g, d_frames.as<double>(), so.s);
-        HIP_OK(hipMemcpy2DAsync(frames_out, frames_stride * sizeof(double), d_frames.p, g.frames * sizeof(double), g.frames * sizeof(double), n_rows,
-                                hipMemcpyDeviceToHost, so.s));
+        rows_to_host(frames_out, frames_stride, d_frames.p, g.frames, g.frames, n_rows, so.s);
         HIP_OK(hipStreamSynchronize(so.s));
         return g.frames;
     } catch (const std::exception& ex) { set_err(std::string("ow_centroid_analyze: ") + ex.what()); return -1; }
@@ -156,35 +144,22 @@ long long ow_centroid_track(const ow_centroid_job* jobs, size_t n_jobs, const ow
         for (size_t i = 0; i < n_jobs; ++i) {
             const ow_centroid_job& j = jobs[i];
             const std::string at = "job " + std::to_string(i) + ": ";
-            if (j.note < OW_MIDI_LO || j.note > OW_MIDI_HI) throw std::runtime_error(at + "note " + std::to_string(j.note) + " outside 33..96 (the tables' range)");
-            if (j.velocity > 127) throw std::runtime_error(at + "velocity " + std::to_string(j.velocity) + " above 127 (a MIDI velocity byte)");
-            if (!(std::isfinite(j.r_ldr) && j.r_ldr > 0.0)) throw std::runtime_error(at + "r_ldr is not a finite positive number");
-            if (!std::isfinite(j.volume)) throw std::runtime_error(at + "volume is not finite");
-            if (!std::isfinite(j.speaker)) throw std::runtime_error(at + "speaker is not finite");
-            if (j.has_displacement_scale && !std::isfinite(j.displacement_scale)) throw std::runtime_error(at + "displacement_scale is not finite");
+            check_note_velocity(at, j.note, j.velocity);
+            check_positive_finite(at, "r_ldr", j.r_ldr);
+            check_finite(at, "volume", j.volume);
+            check_finite(at, "speaker", j.speaker);
+            if (j.has_displacement_scale) check_finite(at, "displacement_scale", j.displacement_scale);
         }
         if (n == 0) {                                      // an empty render: no frame, both "no data" lines
             for (size_t i = 0; i < n_jobs; ++i) centroid::summarise(jobs[i].note, nullptr, g, rows_out[i]);
             return 0;
         }
-        int ndev = 0;
-        HIP_OK(hipGetDeviceCount(&ndev));
-        if (ndev <= 0) throw std::runtime_error("no HIP device: openwurli-hip has no CPU fallback");
-        HIP_OK(hipSetDevice(cfg->device));
-        std::unique_ptr<OwConsts> hc(new OwConsts());
-        owhip::build_consts(*hc, centroid::SR, OW_PREAMP_LEGACY8);     // the preamp at OVERSAMPLED_SR = 88 200 Hz
-        const size_t stride = (n + 63) / 64 * 64;                       // 512-byte aligned rows
+        OfflineCall call(cfg->device, centroid::SR, OW_PREAMP_LEGACY8, /*note_table=*/true);   // the preamp at OVERSAMPLED_SR = 88 200 Hz
+        hipStream_t st = call.st();
+        const size_t stride = (size_t)row_stride((long long)n);
         const size_t row_bytes = sizeof(double) * stride;
-        const Switches sw = Switches::from_env();                       // offline entry point: read once per call
-        size_t chunk = std::max<size_t>(1, centroid::BUDGET_BYTES / (2 * row_bytes));
-        if (sw.centroid_chunk > 0) chunk = std::min(chunk, (size_t)sw.centroid_chunk);
-        chunk = std::min(chunk, n_jobs);
-        StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
-        hipStream_t st = so.s;
-        DevMem m_K, m_nt, m_vrec, m_jobs, m_reed, m_out, m_hann, m_frames;      // released on every exit path
-        m_K.alloc(sizeof(OwConsts));
-        m_nt.alloc(sizeof(double) * NT_COUNT * 64);
+        const size_t chunk = budget_chunk(centroid::BUDGET_BYTES, 2 * row_bytes, call.sw.centroid_chunk, n_jobs);
+        DevMem m_vrec, m_jobs, m_reed, m_out, m_hann, m_frames;         // released on every exit path
         m_vrec.alloc(sizeof(double) * ((chunk + 63) / 64) * OW_VREC_DOUBLES);
         m_jobs.alloc(sizeof(owdev::OwJobDev) * chunk);
         m_reed.alloc(row_bytes * chunk);
@@ -192,11 +167,7 @@ long long ow_centroid_track(const ow_centroid_job* jobs, size_t n_jobs, const ow
         m_frames.alloc(sizeof(double) * chunk * std::max<size_t>(g.frames, 1));
         const std::vector<double> hann = centroid::hann_table(g.window);
         m_hann.alloc(sizeof(double) * hann.size());
-        OwConsts* dK = m_K.as<OwConsts>();
-        HIP_OK(hipMemcpyAsync(dK, hc.get(), sizeof(OwConsts), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(m_hann.p, hann.data(), sizeof(double) * hann.size(), hipMemcpyHostToDevice, st));
-        owdev::k_note_table<<<dim3(1), dim3(64), 0, st>>>(m_nt.as<double>());
-        HIP_OK(hipGetLastError());
         const JobChainCfg cc{centroid::SR, cfg->device, OW_PREAMP_LEGACY8, OW_POWER_AMP_BEHAVIORAL, 0};
         std::vector<owdev::OwJobDev> hj;
         for (size_t c0 = 0; c0 < n_jobs; c0 += chunk) {
@@ -214,17 +185,13 @@ long long ow_centroid_track(const ow_centroid_job* jobs, size_t n_jobs, const ow
                 d.volume = j.volume; d.speaker = j.speaker; d.r_ldr = j.r_ldr; d.tremolo_depth = 0.0;
             }
             HIP_OK(hipMemcpyAsync(m_jobs.p, hj.data(), sizeof(owdev::OwJobDev) * cn, hipMemcpyHostToDevice, st));
-            owdev::k_job_voice<<<dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, st>>>(dK, m_nt.as<double>(), m_vrec.as<double>(), m_jobs.as<owdev::OwJobDev>(),
+            owdev::k_job_voice<<<dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, st>>>(call.dK(), call.nt(), m_vrec.as<double>(), m_jobs.as<owdev::OwJobDev>(),
                                                                                       m_reed.as<double>(), (int)cn, (long long)n, (long long)stride);
             HIP_OK(hipGetLastError());
-            run_job_chain(cc, dK, hj, m_jobs.as<owdev::OwJobDev>(), m_reed.as<double>(), m_out.as<double>(), cn, (long long)n, (long long)stride, st);
+            run_job_chain(call, cc, hj, m_jobs.as<owdev::OwJobDev>(), m_reed.as<double>(), m_out.as<double>(), cn, (long long)n, (long long)stride);
             centroid::launch_frames(m_out.as<double>(), cn, stride, m_hann.as<double>(), g, m_frames.as<double>(), st);
-            if (g.frames > 0)
-                HIP_OK(hipMemcpy2DAsync(frames_out + c0 * frames_stride, frames_stride * sizeof(double), m_frames.p, g.frames * sizeof(double),
-                                        g.frames * sizeof(double), cn, hipMemcpyDeviceToHost, st));
-            if (audio_out)
-                HIP_OK(hipMemcpy2DAsync(audio_out + c0 * audio_stride, audio_stride * sizeof(double), m_out.p, row_bytes, sizeof(double) * n, cn,
-                                        hipMemcpyDeviceToHost, st));
+            if (g.frames > 0) rows_to_host(frames_out + c0 * frames_stride, frames_stride, m_frames.p, g.frames, g.frames, cn, st);
+            if (audio_out) rows_to_host(audio_out + c0 * audio_stride, audio_stride, m_out.p, stride, n, cn, st);
             HIP_OK(hipStreamSynchronize(st));               // the buffers are reused by the next chunk
         }
         for (size_t i = 0; i < n_jobs; ++i) centroid::summarise(jobs[i].note, frames_out ? frames_out + i * frames_stride : nullptr, g, rows_out[i]);

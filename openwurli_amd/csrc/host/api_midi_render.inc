@@ -98,10 +98,8 @@ long long ow_render_midi(const ow_timed_event* events, const size_t* job_offsets
                          double* out, size_t stride, ow_midi_render_stats* stats) {
     try {
         if (!job_offsets || !cfg || (!out && !stats)) throw std::runtime_error("null argument");
-        if (cfg->struct_size != sizeof(ow_midi_render_cfg))
-            throw std::runtime_error("ABI mismatch: ow_midi_render_cfg.struct_size does not match this library's openwurli_hip.h (OW_ABI_VERSION " +
-                                     std::to_string(OW_ABI_VERSION) + ")");
-        if (cfg->preamp_kind != OW_PREAMP_LEGACY8 && cfg->preamp_kind != OW_PREAMP_MELANGE12) throw std::runtime_error("unknown preamp_kind");
+        if (cfg->struct_size != sizeof(ow_midi_render_cfg)) throw std::runtime_error(abi_mismatch("ow_midi_render_cfg.struct_size does"));
+        require_known_kinds(cfg->preamp_kind);           // (power_amp_kind: by run_job_chain)
         if (n_jobs == 0) return 0;
         const double SR = 44100.0;                       // BASE_SR, main.rs:27
         const size_t n_ev = job_offsets[n_jobs];
@@ -118,8 +116,7 @@ long long ow_render_midi(const ow_timed_event* events, const size_t* job_offsets
             std::stable_sort(ev.begin(), ev.end(), [](const ow_timed_event& a, const ow_timed_event& c) { return a.time_s < c.time_s; });   // :1712
             size_t total = 0;
             if (!ev.empty()) {
-                const double x = (ev.back().time_s + cfg->tail_s) * SR;                                                     // :1719-1721
-                total = (!(x == x) || x <= 0.0) ? 0 : (x >= 1.8446744073709552e19 ? SIZE_MAX : (size_t)x);
+                total = rust_as_usize((ev.back().time_s + cfg->tail_s) * SR);                                               // :1719-1721
                 if (total > (size_t)1 << 36) throw std::runtime_error("render longer than 2^36 samples");
             }
             for (size_t i = 0; i < ev.size(); ++i) {
@@ -138,12 +135,7 @@ long long ow_render_midi(const ow_timed_event* events, const size_t* job_offsets
         }
         if (!out || longest == 0) return (long long)longest;
         if (stride < longest) throw std::runtime_error("stride smaller than the longest job");
-        int ndev = 0;
-        HIP_OK(hipGetDeviceCount(&ndev));
-        if (ndev <= 0) throw std::runtime_error("no HIP device: openwurli-hip has no CPU fallback");
-        HIP_OK(hipSetDevice(cfg->device));
-        OwConsts hc;
-        owhip::build_consts(hc, SR, cfg->preamp_kind);
+        OfflineCall call(cfg->device, SR, cfg->preamp_kind, /*note_table=*/true);
         std::vector<owdev::OwJobDev> hjob(n_jobs);       // chain parameters: Speaker(speaker), static 1 Mohm LDR, volume, power amp
         for (auto& q : hjob) {
             std::memset(&q, 0, sizeof q);
@@ -152,12 +144,8 @@ long long ow_render_midi(const ow_timed_event* events, const size_t* job_offsets
             // to the settled clone at the nominal pot (melange_adapter.rs:88-93) and the command never sets it again
             q.r_ldr = cfg->preamp_kind == OW_PREAMP_MELANGE12 ? 9.99999999999999854e4 : 1000000.0;
         }
-        StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
-        hipStream_t st = so.s;
-        DevMem dK, d_nt, d_vrec, d_jobs, d_ev, d_held, d_sum, d_out, d_chain, d_stats;
-        dK.alloc(sizeof(OwConsts));
-        d_nt.alloc(sizeof(double) * NT_COUNT * 64);
+        hipStream_t st = call.st();
+        DevMem d_vrec, d_jobs, d_ev, d_held, d_sum, d_out, d_chain, d_stats;
         d_vrec.alloc(sizeof(double) * n_jobs * OW_VREC_DOUBLES);
         d_jobs.alloc(sizeof(owdev::OwMidiJobDev) * n_jobs);
         d_ev.alloc(sizeof(owdev::OwMidiEvDev) * hev.size());
@@ -166,20 +154,18 @@ long long ow_render_midi(const ow_timed_event* events, const size_t* job_offsets
         d_out.alloc(sizeof(double) * n_jobs * longest);
         d_chain.alloc(sizeof(owdev::OwJobDev) * n_jobs);
         d_stats.alloc(sizeof(owdev::OwMidiStatsDev) * n_jobs);
-        HIP_OK(hipMemcpyAsync(dK.p, &hc, sizeof(OwConsts), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_jobs.p, hj.data(), sizeof(owdev::OwMidiJobDev) * n_jobs, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_ev.p, hev.data(), sizeof(owdev::OwMidiEvDev) * hev.size(), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_chain.p, hjob.data(), sizeof(owdev::OwJobDev) * n_jobs, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemsetAsync(d_sum.p, 0, sizeof(double) * n_jobs * longest, st));   // rows behind a shorter job's end feed the chain zeros
-        owdev::k_note_table<<<dim3(1), dim3(64), 0, st>>>(d_nt.as<double>());
-        owdev::k_midi_voices<<<dim3((unsigned)n_jobs), dim3(64), 0, st>>>(dK.as<OwConsts>(), d_nt.as<double>(), d_vrec.as<double>(), d_jobs.as<owdev::OwMidiJobDev>(),
+        owdev::k_midi_voices<<<dim3((unsigned)n_jobs), dim3(64), 0, st>>>(call.dK(), call.nt(), d_vrec.as<double>(), d_jobs.as<owdev::OwMidiJobDev>(),
                                                                          d_ev.as<owdev::OwMidiEvDev>(), d_held.as<uint32_t>(), d_sum.as<double>(), (long long)longest,
                                                                          d_stats.as<owdev::OwMidiStatsDev>());
         HIP_OK(hipGetLastError());
         const JobChainCfg cc{SR, cfg->device, cfg->preamp_kind, cfg->power_amp_kind, cfg->no_rail_sag};
-        run_job_chain(cc, dK.as<OwConsts>(), hjob, d_chain.as<owdev::OwJobDev>(), d_sum.as<double>(), d_out.as<double>(), n_jobs, (long long)longest, (long long)longest, st);
+        run_job_chain(call, cc, hjob, d_chain.as<owdev::OwJobDev>(), d_sum.as<double>(), d_out.as<double>(), n_jobs, (long long)longest, (long long)longest);
         std::vector<owdev::OwMidiStatsDev> hs(n_jobs);
-        HIP_OK(hipMemcpy2DAsync(out, stride * sizeof(double), d_out.p, longest * sizeof(double), longest * sizeof(double), n_jobs, hipMemcpyDeviceToHost, st));
+        rows_to_host(out, stride, d_out.p, longest, longest, n_jobs, st);
         HIP_OK(hipMemcpyAsync(hs.data(), d_stats.p, sizeof(owdev::OwMidiStatsDev) * n_jobs, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         for (size_t j = 0; j < n_jobs; ++j) {

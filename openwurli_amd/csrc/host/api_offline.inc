@@ -27,8 +27,7 @@ static long long render_note_impl(uint8_t midi, double velocity, double dur_s, d
         e->sync_masks(0);
         push_op(e, OP_NOTE_ON, 0, note, false, (uint32_t)midi * 2654435761u, velocity);
         if (ds) push_op(e, OP_SET_DS, 0, note, false, 0, *ds);      // voice.set_displacement_scale(scale) right after note_on (voice.rs:210-212)
-        double x = dur_s * sample_rate;
-        const size_t n = (!(x == x) || x <= 0.0) ? 0 : (size_t)x;
+        const size_t n = rust_as_usize(dur_s * sample_rate);
         const size_t chunk_len = p->Lcap;            // OW_MAX_BLOCK for a pool of one: few launches, few synchronisations
         std::vector<double> chunk(chunk_len);
         size_t done = 0;
@@ -54,20 +53,12 @@ static long long render_note_impl(uint8_t midi, double velocity, double dur_s, d
 long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg* cfg, double* out, size_t stride, int out_is_device) {
     try {
         if (!jobs || !cfg || !out || n_jobs == 0) throw std::runtime_error("null argument");
-        if (cfg->struct_size != sizeof(ow_batch_cfg) || cfg->job_size != sizeof(ow_job))
-            throw std::runtime_error("ABI mismatch: ow_batch_cfg.struct_size / job_size do not match this library's openwurli_hip.h (OW_ABI_VERSION " +
-                                     std::to_string(OW_ABI_VERSION) + ")");
-        if (cfg->preamp_kind != OW_PREAMP_LEGACY8 && cfg->preamp_kind != OW_PREAMP_MELANGE12) throw std::runtime_error("unknown preamp_kind");
-        const double x = cfg->duration_s * cfg->sample_rate;
-        const size_t n = (!(x == x) || x <= 0.0) ? 0 : (size_t)x;                 // (duration * sample_rate) as usize, main.rs:411
+        if (cfg->struct_size != sizeof(ow_batch_cfg) || cfg->job_size != sizeof(ow_job)) throw std::runtime_error(abi_mismatch("ow_batch_cfg.struct_size / job_size do"));
+        require_known_kinds(cfg->preamp_kind);                                    // (power_amp_kind: by run_job_chain)
+        const size_t n = rust_as_usize(cfg->duration_s * cfg->sample_rate);       // (duration * sample_rate) as usize, main.rs:411
         if (n == 0) return 0;
         if (stride < n) throw std::runtime_error("stride smaller than the job length");
-        int ndev = 0;
-        HIP_OK(hipGetDeviceCount(&ndev));
-        if (ndev <= 0) throw std::runtime_error("no HIP device: openwurli-hip has no CPU fallback");
-        HIP_OK(hipSetDevice(cfg->device));
-        OwConsts hc;
-        owhip::build_consts(hc, cfg->sample_rate, cfg->preamp_kind);
+        OfflineCall call(cfg->device, cfg->sample_rate, cfg->preamp_kind, /*note_table=*/true);
         std::vector<owdev::OwJobDev> hj(n_jobs);
         for (size_t i = 0; i < n_jobs; ++i) {
             hj[i].note = jobs[i].note; hj[i].velocity = jobs[i].velocity; hj[i].mlp = jobs[i].mlp; hj[i].poweramp = jobs[i].poweramp;
@@ -77,22 +68,16 @@ long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg*
             hj[i].tremolo_depth = jobs[i].tremolo_depth; hj[i].displacement_scale = jobs[i].displacement_scale;
         }
         const size_t vblocks = (n_jobs + 63) / 64;
-        StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
-        hipStream_t st = so.s;
-        DevMem m_K, m_nt, m_vrec, m_jobs, m_reed, m_out;   // released on every exit path
-        m_K.alloc(sizeof(OwConsts));
-        m_nt.alloc(sizeof(double) * NT_COUNT * 64);
+        hipStream_t st = call.st();
+        DevMem m_vrec, m_jobs, m_reed, m_out;              // released on every exit path
         m_vrec.alloc(sizeof(double) * vblocks * OW_VREC_DOUBLES);
         m_jobs.alloc(sizeof(owdev::OwJobDev) * n_jobs);
         m_reed.alloc(sizeof(double) * n_jobs * stride);      // same row stride as the output: the chain kernels index both with it
         if (!out_is_device) m_out.alloc(sizeof(double) * n_jobs * stride);
-        OwConsts* dK = m_K.as<OwConsts>(); double* d_nt = m_nt.as<double>(); double* d_vrec = m_vrec.as<double>();
+        const OwConsts* dK = call.dK(); const double* d_nt = call.nt(); double* d_vrec = m_vrec.as<double>();
         owdev::OwJobDev* d_jobs = m_jobs.as<owdev::OwJobDev>(); double* d_reed = m_reed.as<double>();
         double* d_out = out_is_device ? out : m_out.as<double>();
-        HIP_OK(hipMemcpyAsync(dK, &hc, sizeof(OwConsts), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_jobs, hj.data(), sizeof(owdev::OwJobDev) * n_jobs, hipMemcpyHostToDevice, st));
-        owdev::k_note_table<<<dim3(1), dim3(64), 0, st>>>(d_nt);
         const JobChainCfg cc{cfg->sample_rate, cfg->device, cfg->preamp_kind, cfg->power_amp_kind, cfg->no_rail_sag};
         // Voices and chain side by side when the chain is the plain legacy one and leaves room on the chip: a job's run time is serial
         // latency in both kernels, so the 13 % the voices take are hidden behind the chain instead of in front of it.
@@ -118,13 +103,13 @@ long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg*
             owdev::k_job_voice<<<dim3((unsigned)vblocks), dim3(64), 0, st>>>(dK, d_nt, d_vrec, d_jobs, d_reed, (int)n_jobs, (long long)n, (long long)stride);
             HIP_OK(hipGetLastError());
         }
-        run_job_chain(cc, dK, hj, d_jobs, d_reed, d_out, n_jobs, (long long)n, (long long)stride, st, d_prog);
+        run_job_chain(call, cc, hj, d_jobs, d_reed, d_out, n_jobs, (long long)n, (long long)stride, d_prog);
         if (overlap) {
             HIP_OK(hipStreamWaitEvent(st, ev_voice, 0));
             int gave_up = 0;
             HIP_OK(hipMemcpyAsync(&gave_up, d_prog + vblocks, sizeof(int), hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
-            if (gave_up) run_job_chain(cc, dK, hj, d_jobs, d_reed, d_out, n_jobs, (long long)n, (long long)stride, st);   // the voices are complete now
+            if (gave_up) run_job_chain(call, cc, hj, d_jobs, d_reed, d_out, n_jobs, (long long)n, (long long)stride);   // the voices are complete now
         }
         if (!out_is_device) HIP_OK(hipMemcpyAsync(out, d_out, sizeof(double) * n_jobs * stride, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));

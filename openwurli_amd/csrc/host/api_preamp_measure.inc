@@ -2,21 +2,9 @@
 // `sweep` / `harmonics` / `tremolo-sweep`, tools/preamp-bench/src/main.rs:150-369).
 namespace {
 namespace pbench {
-inline bool positive_finite(double x) { return std::isfinite(x) && x > 0.0; }
 // OW_PBENCH_ROW=0/1 forces the kernel; otherwise a row of sixteen lanes per solver state (k_pbench_row: five wavefronts per eight points)
 // while the grid leaves the chip's SIMDs free, the lane pair (k_pbench<false>: one wavefront per 32 points) beyond -- as job_chain_row()
 inline bool use_row(size_t n_pts, int forced) { return forced >= 0 ? forced != 0 : n_pts <= 1024; }
-// points per launch: all of them without a trace; with one, a device trace buffer of ~4 GiB ([chunk][stride] f64).  cap > 0 (the
-// OW_PBENCH_CHUNK switch, tests) caps either.
-inline size_t chunk_points(size_t n_pts, bool trace, size_t row_bytes, long long cap) {
-    size_t c = trace ? std::max<size_t>((size_t(4) << 30) / row_bytes, 1) : n_pts;
-    if (cap > 0) c = std::min(c, (size_t)cap);
-    return std::max<size_t>(std::min(c, n_pts), 1);
-}
-inline double dft_magnitude(double re, double im, double n) {          // main.rs:893-903 (the sums come from the kernel)
-    const double a = re / n, b = im / n;
-    return 2.0 * std::sqrt(a * a + b * b);
-}
 }  // namespace pbench
 }  // namespace
 
@@ -26,48 +14,37 @@ int ow_preamp_measure(const ow_preamp_point* points, size_t n_pts, const ow_prea
     try {
         if (!cfg) throw std::runtime_error("null argument");
         if (cfg->struct_size != sizeof(ow_preamp_measure_cfg) || cfg->point_size != sizeof(ow_preamp_point))
-            throw std::runtime_error("ABI mismatch: ow_preamp_measure_cfg.struct_size / point_size do not match this library's openwurli_hip.h (OW_ABI_VERSION " +
-                                     std::to_string(OW_ABI_VERSION) + ")");
+            throw std::runtime_error(abi_mismatch("ow_preamp_measure_cfg.struct_size / point_size do"));
         if (n_pts == 0) return 0;
         if (!points || !rows_out) throw std::runtime_error("null argument");
-        if (cfg->preamp_kind != OW_PREAMP_LEGACY8 && cfg->preamp_kind != OW_PREAMP_MELANGE12) throw std::runtime_error("unknown preamp_kind");
+        require_known_kinds(cfg->preamp_kind);
         const long long n = OW_PBENCH_SAMPLES;
         if (trace_out && trace_stride < (size_t)n) throw std::runtime_error("trace_stride smaller than " + std::to_string(n));
         if (n_pts > (size_t)INT32_MAX) throw std::runtime_error("too many points");
         std::vector<owdev::OwPbenchDev> hp(n_pts);
         for (size_t i = 0; i < n_pts; ++i) {
             const ow_preamp_point& q = points[i];
-            const char* bad = !pbench::positive_finite(q.freq_hz) ? "freq_hz" : !pbench::positive_finite(q.amplitude) ? "amplitude"
-                            : !pbench::positive_finite(q.r_ldr) ? "r_ldr" : !pbench::positive_finite(q.r_reset) ? "r_reset" : nullptr;
-            if (bad) throw std::runtime_error("point " + std::to_string(i) + ": " + bad + " is not a finite positive number");
+            const std::string at = "point " + std::to_string(i) + ": ";
+            check_positive_finite(at, "freq_hz", q.freq_hz); check_positive_finite(at, "amplitude", q.amplitude);
+            check_positive_finite(at, "r_ldr", q.r_ldr); check_positive_finite(at, "r_reset", q.r_reset);
             hp[i].freq = q.freq_hz; hp[i].amp = q.amplitude; hp[i].r_ldr = q.r_ldr; hp[i].r_reset = q.r_reset;
         }
-        int ndev = 0;
-        HIP_OK(hipGetDeviceCount(&ndev));
-        if (ndev <= 0) throw std::runtime_error("no HIP device: openwurli-hip has no CPU fallback");
-        HIP_OK(hipSetDevice(cfg->device));
-        std::unique_ptr<OwConsts> hc(new OwConsts());
-        owhip::build_consts(*hc, 44100.0, cfg->preamp_kind);            // BASE_SR: the preamp at OVERSAMPLED_SR = 88 200 Hz (main.rs:27-28)
+        OfflineCall call(cfg->device, 44100.0, cfg->preamp_kind, /*note_table=*/false);   // BASE_SR: the preamp at OVERSAMPLED_SR = 88 200 Hz (main.rs:27-28)
+        hipStream_t st = call.st();
+        const OwConsts* dK = call.dK();
+        const Switches& sw = call.sw;
         const bool mel = cfg->preamp_kind == OW_PREAMP_MELANGE12;
-        const long long stride = (n + 63) / 64 * 64;                   // 512-byte aligned trace rows
+        const long long stride = row_stride(n);
         const size_t row_bytes = sizeof(double) * (size_t)stride;
-        const Switches sw = Switches::from_env();                      // offline entry point: read once per call
-        const size_t chunk = pbench::chunk_points(n_pts, trace_out != nullptr, row_bytes, sw.pbench_chunk);
-        StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
-        hipStream_t st = so.s;
-        DevMem m_K, m_pts, m_met, m_trace, m_settled;                  // released on every exit path
-        m_K.alloc(sizeof(OwConsts));
+        // points per launch: with a trace, a device trace buffer of ~4 GiB ([chunk][stride] f64); without one nothing is kept per point
+        // but its metrics -- all points in one launch
+        const size_t chunk = trace_out ? budget_chunk(size_t(4) << 30, row_bytes, sw.pbench_chunk, n_pts) : budget_chunk(SIZE_MAX, 1, sw.pbench_chunk, n_pts);
+        DevMem m_pts, m_met, m_trace;                                  // released on every exit path
         m_pts.alloc(sizeof(owdev::OwPbenchDev) * n_pts);
         m_met.alloc(sizeof(double) * owdev::PB_MET_COUNT * n_pts);
         if (trace_out) m_trace.alloc(row_bytes * chunk);
-        OwConsts* dK = m_K.as<OwConsts>();
-        HIP_OK(hipMemcpyAsync(dK, hc.get(), sizeof(OwConsts), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(m_pts.p, hp.data(), sizeof(owdev::OwPbenchDev) * n_pts, hipMemcpyHostToDevice, st));
-        if (mel) {                                                     // reset() / new() clone the settled state (melange_adapter.rs:22-29, 88-93)
-            m_settled.alloc(sizeof(double) * 18);
-            mel_settled_to_device(cfg->device, m_settled.as<double>(), st);
-        }
+        const double* settled = mel ? call.mel_settled() : nullptr;
         for (size_t p0 = 0; p0 < n_pts; p0 += chunk) {
             const size_t cn = std::min(chunk, n_pts - p0);
             const int ci = (int)cn;
@@ -75,15 +52,13 @@ int ow_preamp_measure(const ow_preamp_point* points, size_t n_pts, const ow_prea
             double* met = m_met.as<double>() + p0 * owdev::PB_MET_COUNT;
             double* tr = trace_out ? m_trace.as<double>() : nullptr;
             if (mel)
-                owdev::k_pbench<true><<<dim3((unsigned)((cn + 31) / 32)), dim3(64), 0, st>>>(dK, cp, met, tr, m_settled.as<double>(), ci, stride);
+                owdev::k_pbench<true><<<dim3((unsigned)((cn + 31) / 32)), dim3(64), 0, st>>>(dK, cp, met, tr, settled, ci, stride);
             else if (pbench::use_row(cn, sw.pbench_row))
                 owdev::k_pbench_row<<<dim3((unsigned)((cn + 7) / 8)), dim3(320), 0, st>>>(dK, cp, met, tr, ci, stride);
             else
                 owdev::k_pbench<false><<<dim3((unsigned)((cn + 31) / 32)), dim3(64), 0, st>>>(dK, cp, met, tr, nullptr, ci, stride);
             HIP_OK(hipGetLastError());
-            if (trace_out)
-                HIP_OK(hipMemcpy2DAsync(trace_out + p0 * trace_stride, trace_stride * sizeof(double), tr, row_bytes, sizeof(double) * (size_t)n, cn,
-                                        hipMemcpyDeviceToHost, st));
+            if (trace_out) rows_to_host(trace_out + p0 * trace_stride, trace_stride, tr, (size_t)stride, (size_t)n, cn, st);
         }
         std::vector<double> hm(n_pts * owdev::PB_MET_COUNT);
         HIP_OK(hipMemcpyAsync(hm.data(), m_met.p, sizeof(double) * hm.size(), hipMemcpyDeviceToHost, st));
@@ -97,7 +72,7 @@ int ow_preamp_measure(const ow_preamp_point* points, size_t n_pts, const ow_prea
             r.freq_hz = q.freq_hz; r.amplitude = q.amplitude; r.r_ldr = q.r_ldr;
             r.gain = m[owdev::PB_MET_PEAK] / q.amplitude;                                         // measure_gain_at, main.rs:189
             r.gain_db = 20.0 * std::log10(r.gain);                                                // cmd_gain / cmd_sweep, :199, :238
-            for (int k = 0; k < 5; ++k) r.h[k] = pbench::dft_magnitude(m[owdev::PB_MET_RE1 + 2 * k], m[owdev::PB_MET_RE1 + 2 * k + 1], nh);
+            for (int k = 0; k < 5; ++k) r.h[k] = measure::dft_magnitude(m[owdev::PB_MET_RE1 + 2 * k], m[owdev::PB_MET_RE1 + 2 * k + 1], nh);
             const double h1 = r.h[0], h2 = r.h[1], h3 = r.h[2], h4 = r.h[3], h5 = r.h[4];    // cmd_harmonics, :292-298
             r.thd_pct = (std::sqrt(h2 * h2 + h3 * h3 + h4 * h4 + h5 * h5) / h1) * 100.0;
             r.h2_h3_db = h3 > 1e-15 ? 20.0 * std::log10(h2 / h3) : INFINITY;

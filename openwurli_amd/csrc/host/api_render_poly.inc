@@ -2,9 +2,6 @@
 // (tools/preamp-bench/src/main.rs:1397-1592), the chord intermodulation measurement, for many chords per call.
 namespace {
 namespace poly {
-// main.rs:916-927, 2241-2247 (the peaks and sums come from k_poly_chain)
-inline double to_dbfs(double val) { return val > 1e-15 ? 20.0 * std::log10(val) : -120.0; }
-inline double rms_db(double mean_sq) { return mean_sq > 0.0 ? 10.0 * std::log10(mean_sq) : -120.0; }
 // device rows a chord takes: its n voice rows plus final, separate_sum, residual
 inline size_t chord_rows(const ow_poly_chord& c) { return (size_t)c.n_notes + 3; }
 const size_t BUDGET_BYTES = size_t(8) << 30;      // per chunk, as the calibration sweep's
@@ -17,18 +14,12 @@ long long ow_render_poly(const ow_poly_chord* chords, size_t n_chords, const ow_
     try {
         if (!cfg) throw std::runtime_error("null argument");
         if (cfg->struct_size != sizeof(ow_poly_cfg) || cfg->chord_size != sizeof(ow_poly_chord))
-            throw std::runtime_error("ABI mismatch: ow_poly_cfg.struct_size / chord_size do not match this library's openwurli_hip.h (OW_ABI_VERSION " +
-                                     std::to_string(OW_ABI_VERSION) + ")");
-        if (cfg->preamp_kind == OW_PREAMP_MELANGE12)
-            throw std::runtime_error("preamp_kind OW_PREAMP_MELANGE12 is not supported: the melange preamp's reset() discards --ldr (see openwurli_hip.h)");
-        if (cfg->preamp_kind != OW_PREAMP_LEGACY8) throw std::runtime_error("unknown preamp_kind");
-        if (cfg->power_amp_kind == OW_POWER_AMP_MELANGE)
-            throw std::runtime_error("power_amp_kind OW_POWER_AMP_MELANGE is not supported: it needs its own launch between the stages (see openwurli_hip.h)");
-        if (cfg->power_amp_kind != OW_POWER_AMP_BEHAVIORAL) throw std::runtime_error("unknown power_amp_kind");
+            throw std::runtime_error(abi_mismatch("ow_poly_cfg.struct_size / chord_size do"));
+        require_legacy_chain(cfg->preamp_kind, cfg->power_amp_kind);
         const double sr = 44100.0;                                     // BASE_SR, main.rs:27
-        const double x = cfg->duration_s * sr;
         // (duration * BASE_SR) as usize (main.rs:1422); the window slice [8820, min(88200, n)) panics in the reference unless n > 8820 (:1516-1520)
-        const long long n = (x == x && x > 0.0 && x < 2147483648.0) ? (long long)x : 0;
+        const size_t nu = rust_as_usize(cfg->duration_s * sr);
+        const long long n = nu < 2147483648ull ? (long long)nu : 0;
         if (n <= OW_POLY_WIN_LO)
             throw std::runtime_error("duration_s must give more than " + std::to_string(OW_POLY_WIN_LO) + " (and fewer than 2^31) samples: the measurement window starts there");
         const bool any_audio = final_out || separate_sum_out || residual_out;
@@ -41,24 +32,17 @@ long long ow_render_poly(const ow_poly_chord* chords, size_t n_chords, const ow_
             const std::string at = "chord " + std::to_string(i) + ": ";
             if (c.n_notes < 1 || c.n_notes > OW_POLY_MAX_NOTES)
                 throw std::runtime_error(at + "n_notes " + std::to_string(c.n_notes) + " outside 1.." + std::to_string(OW_POLY_MAX_NOTES));
-            for (int k = 0; k < c.n_notes; ++k) {
-                if (c.notes[k] < OW_MIDI_LO || c.notes[k] > OW_MIDI_HI)
-                    throw std::runtime_error(at + "note " + std::to_string(c.notes[k]) + " outside 33..96 (the tables' range)");
-                if (c.velocities[k] > 127) throw std::runtime_error(at + "velocity " + std::to_string(c.velocities[k]) + " above 127 (a MIDI velocity byte)");
-            }
-            if (!(std::isfinite(c.r_ldr) && c.r_ldr > 0.0)) throw std::runtime_error(at + "r_ldr is not a finite positive number");
-            if (!std::isfinite(c.volume)) throw std::runtime_error(at + "volume is not finite");
-            if (!std::isfinite(c.speaker)) throw std::runtime_error(at + "speaker is not finite");
+            for (int k = 0; k < c.n_notes; ++k) check_note_velocity(at, c.notes[k], c.velocities[k]);
+            check_positive_finite(at, "r_ldr", c.r_ldr);
+            check_finite(at, "volume", c.volume);
+            check_finite(at, "speaker", c.speaker);
         }
-        int ndev = 0;
-        HIP_OK(hipGetDeviceCount(&ndev));
-        if (ndev <= 0) throw std::runtime_error("no HIP device: openwurli-hip has no CPU fallback");
-        HIP_OK(hipSetDevice(cfg->device));
-        std::unique_ptr<OwConsts> hc(new OwConsts());
-        owhip::build_consts(*hc, sr, OW_PREAMP_LEGACY8);               // the preamp at OVERSAMPLED_SR = 88 200 Hz (main.rs:27-28, 132-148)
-        const long long stride = (n + 63) / 64 * 64;                   // 512-byte aligned rows
+        OfflineCall call(cfg->device, sr, OW_PREAMP_LEGACY8, /*note_table=*/true);   // the preamp at OVERSAMPLED_SR = 88 200 Hz (main.rs:27-28, 132-148)
+        hipStream_t st = call.st();
+        const OwConsts* dK = call.dK();
+        const Switches& sw = call.sw;
+        const long long stride = row_stride(n);
         const size_t row_bytes = sizeof(double) * (size_t)stride;
-        const Switches sw = Switches::from_env();                      // offline entry point: read once per call
         // chunks: runs of chords in call order whose rows (n voice rows + three result rows each) fit the budget, OW_POLY_CHUNK chords at most
         std::vector<size_t> cuts{0};
         size_t max_chords = 0, max_voices = 0;
@@ -75,12 +59,7 @@ long long ow_render_poly(const ow_poly_chord* chords, size_t n_chords, const ow_
             }
             cuts.push_back(n_chords);
         }
-        StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
-        hipStream_t st = so.s;
-        DevMem m_K, m_nt, m_vrec, m_voices, m_chords, m_slots, m_reed, m_fin, m_sep, m_res, m_met;   // released on every exit path
-        m_K.alloc(sizeof(OwConsts));
-        m_nt.alloc(sizeof(double) * NT_COUNT * 64);
+        DevMem m_vrec, m_voices, m_chords, m_slots, m_reed, m_fin, m_sep, m_res, m_met;   // released on every exit path
         m_vrec.alloc(sizeof(double) * ((max_voices + 63) / 64) * OW_VREC_DOUBLES);
         m_voices.alloc(sizeof(owdev::OwPolyVoiceDev) * max_voices);
         m_chords.alloc(sizeof(owdev::OwPolyChordDev) * max_chords);
@@ -90,10 +69,6 @@ long long ow_render_poly(const ow_poly_chord* chords, size_t n_chords, const ow_
         if (separate_sum_out) m_sep.alloc(row_bytes * max_chords);
         if (residual_out) m_res.alloc(row_bytes * max_chords);
         m_met.alloc(sizeof(double) * owdev::POLY_MET_COUNT * n_chords);
-        OwConsts* dK = m_K.as<OwConsts>();
-        HIP_OK(hipMemcpyAsync(dK, hc.get(), sizeof(OwConsts), hipMemcpyHostToDevice, st));
-        owdev::k_note_table<<<dim3(1), dim3(64), 0, st>>>(m_nt.as<double>());
-        HIP_OK(hipGetLastError());
         const long long win_hi = std::min<long long>(OW_POLY_WIN_HI, n);     // (2.0 * BASE_SR).min(n_samples as f64) as usize, main.rs:1517
         std::vector<owdev::OwPolyVoiceDev> hv;
         std::vector<owdev::OwPolyChordDev> hch;
@@ -128,7 +103,7 @@ long long ow_render_poly(const ow_poly_chord* chords, size_t n_chords, const ow_
             HIP_OK(hipMemcpyAsync(m_voices.p, hv.data(), sizeof(owdev::OwPolyVoiceDev) * nv, hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(m_chords.p, hch.data(), sizeof(owdev::OwPolyChordDev) * cn, hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(m_slots.p, hs.data(), sizeof(owdev::OwPolySlotDev) * hs.size(), hipMemcpyHostToDevice, st));
-            owdev::k_poly_voice<<<dim3((unsigned)((nv + 63) / 64)), dim3(64), 0, st>>>(dK, m_nt.as<double>(), m_vrec.as<double>(), m_voices.as<owdev::OwPolyVoiceDev>(),
+            owdev::k_poly_voice<<<dim3((unsigned)((nv + 63) / 64)), dim3(64), 0, st>>>(dK, call.nt(), m_vrec.as<double>(), m_voices.as<owdev::OwPolyVoiceDev>(),
                                                                                         m_reed.as<double>(), (int)nv, n, stride);
             HIP_OK(hipGetLastError());
             owdev::k_poly_chain<<<dim3((unsigned)nblocks), dim3(64), 0, st>>>(dK, m_chords.as<owdev::OwPolyChordDev>(), m_slots.as<owdev::OwPolySlotDev>(),
@@ -136,9 +111,7 @@ long long ow_render_poly(const ow_poly_chord* chords, size_t n_chords, const ow_
                                                                               m_met.as<double>() + c0 * owdev::POLY_MET_COUNT, n, stride, win_hi);
             HIP_OK(hipGetLastError());
             auto copy_rows = [&](double* host, const DevMem& m) {
-                if (host)
-                    HIP_OK(hipMemcpy2DAsync(host + c0 * out_stride, out_stride * sizeof(double), m.p, row_bytes, sizeof(double) * (size_t)n, cn,
-                                            hipMemcpyDeviceToHost, st));
+                if (host) rows_to_host(host + c0 * out_stride, out_stride, m.p, (size_t)stride, (size_t)n, cn, st);
             };
             copy_rows(final_out, m_fin); copy_rows(separate_sum_out, m_sep); copy_rows(residual_out, m_res);
             HIP_OK(hipStreamSynchronize(st));                          // the host vectors are refilled for the next chunk
@@ -156,8 +129,8 @@ long long ow_render_poly(const ow_poly_chord* chords, size_t n_chords, const ow_
             for (int k = 0; k < 3; ++k) {
                 r.win_peak[k] = m[owdev::POLY_MET_WPK + k];
                 r.win_mean_sq[k] = m[owdev::POLY_MET_WSS + k] / nwin;                 // rms_db's mean_sq, main.rs:921
-                r.peak_db[k] = poly::to_dbfs(r.win_peak[k]);                          // :1522-1524
-                r.rms_db[k] = poly::rms_db(r.win_mean_sq[k]);                         // :1525-1527
+                r.peak_db[k] = measure::to_dbfs(r.win_peak[k]);                          // :1522-1524
+                r.rms_db[k] = measure::rms_db(r.win_mean_sq[k]);                         // :1525-1527
             }
             r.intermod_ratio_db = r.rms_db[0] - r.rms_db[2];                          // :1575
         }

@@ -219,8 +219,8 @@ struct Switches {
         if (const char* e = std::getenv("OW_CALIB_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.calib_chunk = v; }
         if (const char* e = std::getenv("OW_PBENCH_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.pbench_chunk = v; }
         if (const char* e = std::getenv("OW_POLY_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.poly_chunk = v; }
-if (const char* e = std::getenv("OW_CENTROID_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.centroid_chunk = v; }
-                w.pbench_row = flag("OW_PBENCH_ROW", -1); if (w.pbench_row > 1 || w.pbench_row < -1) w.pbench_row = -1;
+        if (const char* e = std::getenv("OW_CENTROID_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.centroid_chunk = v; }
+        w.pbench_row = flag("OW_PBENCH_ROW", -1); if (w.pbench_row > 1 || w.pbench_row < -1) w.pbench_row = -1;
         return w;
     }
 };

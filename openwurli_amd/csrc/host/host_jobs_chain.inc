@@ -46,7 +46,6 @@ static void launch_job_chain_legacy(const OwConsts* dK, const owdev::OwJobDev* d
 
 ow_pool* pool_create(double sample_rate, size_t n_engines, int device, int preamp_kind, int power_amp_kind, int tremolo_kind, bool voices_only, bool no_traj = false);
 void pool_destroy(ow_pool* p);
-void pa_settled_to_device(int device, double* d_dst, hipStream_t st);
 
 // The chain of the job paths (`preamp-bench render` / `render-midi`, tools/preamp-bench/src/main.rs:413-497, 1880-1890) for n_jobs rows
 // of voice signal d_in -> d_out (both [n_jobs][stride]), with everything the commands' flags can ask for:
@@ -55,8 +54,9 @@ void pa_settled_to_device(int device, double* d_dst, hipStream_t st);
 //     applies its own depth divider;
 //   * the melange preamp (`--features melange-preamp` build) through k_job_chain<true>;
 //   * the melange power amp (a build without `legacy-power-amp`): PowerAmp::new() is new_at_sample_rate(44 100) whatever the render's
-//     rate is (power_amp.rs:321-323), it runs at the BASE rate on preamp x volume^2 -- as its own launch (eight lanes per job,
-//     k_mpa_debug) between the chain kernel and the speaker stage.
+//     rate is (power_amp.rs:321-323), it runs at the BASE rate on preamp x volume^2 -- as its own launch (MelPowerAmpStage) between the
+//     chain kernel and the speaker stage.
+// `call` is the entry point's OfflineCall at cfg.sample_rate / cfg.preamp_kind: its stream, constants and switches.
 struct JobChainCfg { double sample_rate; int device, preamp_kind, power_amp_kind, no_rail_sag; };
 // true when run_job_chain will take the plain legacy chain (launch_job_chain_legacy) for these jobs
 static bool job_chain_is_plain_legacy(const JobChainCfg& cfg, const std::vector<owdev::OwJobDev>& hj) {
@@ -68,10 +68,11 @@ static bool job_chain_is_plain_legacy(const JobChainCfg& cfg, const std::vector<
     }
     return !(cfg.power_amp_kind == OW_POWER_AMP_MELANGE && any_pa);
 }
-void run_job_chain(const JobChainCfg& cfg, const OwConsts* dK, const std::vector<owdev::OwJobDev>& hj, const owdev::OwJobDev* d_jobs, const double* d_in,
-                   double* d_out, size_t n_jobs, long long n, long long stride, hipStream_t st, const int* voice_prog = nullptr) {
-    if (cfg.preamp_kind != OW_PREAMP_LEGACY8 && cfg.preamp_kind != OW_PREAMP_MELANGE12) throw std::runtime_error("unknown preamp_kind");
-    if (cfg.power_amp_kind != OW_POWER_AMP_BEHAVIORAL && cfg.power_amp_kind != OW_POWER_AMP_MELANGE) throw std::runtime_error("unknown power_amp_kind");
+void run_job_chain(OfflineCall& call, const JobChainCfg& cfg, const std::vector<owdev::OwJobDev>& hj, const owdev::OwJobDev* d_jobs, const double* d_in,
+                   double* d_out, size_t n_jobs, long long n, long long stride, const int* voice_prog = nullptr) {
+    require_known_kinds(cfg.preamp_kind, cfg.power_amp_kind);
+    const OwConsts* dK = call.dK();
+    hipStream_t st = call.st();
     bool any_trem = false, any_special = false, any_pa = false;
     for (const auto& j : hj) {
         any_trem = any_trem || (j.tremolo_depth > 0.0 && !j.no_preamp);
@@ -79,14 +80,14 @@ void run_job_chain(const JobChainCfg& cfg, const OwConsts* dK, const std::vector
         any_pa = any_pa || j.poweramp;
     }
     const bool mpa = cfg.power_amp_kind == OW_POWER_AMP_MELANGE && any_pa;
-    DevMem d_r, d_settled, d_att, d_amp, d_pac, d_pas;
+    DevMem d_r, d_att, d_amp;
     std::shared_ptr<TremTraj> traj;
     const double* trem = nullptr;
     if (any_trem) {
         // Tremolo::new(depth, preamp rate) without a warm-up: every job's cell starts at t = 0 of the shared trajectory of this chain rate
         const bool os = cfg.sample_rate < 88200.0;
         const long long n_os = n * (os ? 2 : 1);
-        const Switches sw = Switches::from_env();          // offline entry point: read once per call
+        const Switches& sw = call.sw;
         if (sw.trem_traj) {
             std::unique_ptr<OwConsts> hc(new OwConsts()), k48(new OwConsts());
             owhip::build_consts(*hc, cfg.sample_rate, OW_PREAMP_LEGACY8);
@@ -118,9 +119,7 @@ void run_job_chain(const JobChainCfg& cfg, const OwConsts* dK, const std::vector
     }
     const int out_mode = mpa ? owdev::JOB_OUT_PA_INPUT : owdev::JOB_OUT_FINAL;
     if (cfg.preamp_kind == OW_PREAMP_MELANGE12) {
-        d_settled.alloc(sizeof(double) * 18);
-        mel_settled_to_device(cfg.device, d_settled.as<double>(), st);
-        owdev::k_job_chain<true><<<dim3((unsigned)((n_jobs + 31) / 32)), dim3(64), 0, st>>>(dK, d_jobs, d_in, chain_out, d_settled.as<double>(), (int)n_jobs, n, stride,
+        owdev::k_job_chain<true><<<dim3((unsigned)((n_jobs + 31) / 32)), dim3(64), 0, st>>>(dK, d_jobs, d_in, chain_out, call.mel_settled(), (int)n_jobs, n, stride,
                                                                                             trem, out_mode);
     } else if (!any_trem && !any_special && !mpa) {
         launch_job_chain_legacy(dK, d_jobs, d_in, chain_out, n_jobs, n, stride, st, voice_prog);
@@ -129,18 +128,11 @@ void run_job_chain(const JobChainCfg& cfg, const OwConsts* dK, const std::vector
     }
     HIP_OK(hipGetLastError());
     if (mpa) {
-        std::unique_ptr<OwPaConsts> hpa(new OwPaConsts());
-        owhip::build_pa_consts(*hpa, 44100.0);
-        d_pac.alloc(sizeof(OwPaConsts));
-        d_pas.alloc(sizeof(double) * owdev::PAS_CIRCUIT_END);
-        pa_settled_to_device(cfg.device, d_pas.as<double>(), st);
-        HIP_OK(hipMemcpyAsync(d_pac.p, hpa.get(), sizeof(OwPaConsts), hipMemcpyHostToDevice, st));
-        owdev::k_mpa_debug<<<dim3((unsigned)((n_jobs + PA_EPB - 1) / PA_EPB)), dim3(PA_WPB * 64), 0, st>>>(d_pac.as<OwPaConsts>(), d_pas.as<double>(), d_att.as<double>(),
-                                                                                                       d_amp.as<double>(), nullptr, n, (int)n_jobs, cfg.no_rail_sag ? 0 : 1,
-                                                                                                       nullptr, nullptr, nullptr, stride);
+        MelPowerAmpStage pa(cfg.device, st);
+        pa.run(d_att.as<double>(), d_amp.as<double>(), n, (int)n_jobs, cfg.no_rail_sag ? 0 : 1, stride);
         owdev::k_job_speaker<<<dim3((unsigned)((n_jobs + 63) / 64)), dim3(64), 0, st>>>(dK, d_jobs, d_att.as<double>(), d_amp.as<double>(), d_out, (int)n_jobs, n, stride);
         HIP_OK(hipGetLastError());
-        HIP_OK(hipStreamSynchronize(st));      // hpa and the staging buffers go out of scope
+        HIP_OK(hipStreamSynchronize(st));      // the stage and the staging buffers go out of scope
     }
     HIP_OK(hipStreamSynchronize(st));
 }

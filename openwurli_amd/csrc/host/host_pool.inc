@@ -1002,12 +1002,8 @@ ow_pool* pool_create(double sample_rate, size_t n_engines, int device, int pream
                      int tremolo_kind = OW_TREMOLO_TWIN_T, bool voices_only = false, bool no_traj) {
     if (!(sample_rate > 0.0) || n_engines == 0) throw std::runtime_error("invalid sample rate or engine count");
     if (tremolo_kind != OW_TREMOLO_TWIN_T && tremolo_kind != OW_TREMOLO_LEGACY_LFO) throw std::runtime_error("unknown tremolo_kind");
-    if (preamp_kind != OW_PREAMP_LEGACY8 && preamp_kind != OW_PREAMP_MELANGE12) throw std::runtime_error("unknown preamp_kind");
-    if (power_amp_kind != OW_POWER_AMP_BEHAVIORAL && power_amp_kind != OW_POWER_AMP_MELANGE) throw std::runtime_error("unknown power_amp_kind");
-    int ndev = 0;
-    HIP_OK(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) throw std::runtime_error("no HIP device: openwurli-hip has no CPU fallback");
-    HIP_OK(hipSetDevice(device));
+    require_known_kinds(preamp_kind, power_amp_kind);
+    require_device(device);
     ow_pool* p = new ow_pool();
     p->device = device;
     p->I = n_engines;

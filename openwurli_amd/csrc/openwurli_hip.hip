@@ -55,6 +55,7 @@ using owdev::OwEngineOut;
 #include "host/host_types.inc"          // ow_engine / ow_pool: the host side of one engine and of a pool
 #include "host/host_settle.inc"         // voice-pool mirror synchronisation, process-wide settled states (melange preamp / power amp, Twin-T)
 #include "host/host_trajectory.inc"     // the shared Twin-T / CdS trajectory store (TremTraj), its helper thread, traj_acquire
+#include "host/host_offline.inc"        // what the offline entry points share: refusals, row geometry and chunking, OfflineCall, the melange power amp stage
 #include "host/host_jobs_chain.inc"     // kernel choice for the job paths and the job chain (batch render, render-midi)
 #include "host/host_pool.inc"           // tremolo phase groups, chain (re)initialisation, voice lists, render_range, post-render bookkeeping, pool life cycle
 #include "host/api_pool.inc"            // C-ABI: library / pool entry points, host blocks, taps, trajectory control and persistence, MIDI bursts

@@ -100,11 +100,7 @@ __global__ __launch_bounds__(64) void k_calib_out(const OwConsts* __restrict__ K
         for (long long i = 0; i < n; ++i) y[i] = x[i] * volume * volume;              // audio taper
         return;
     }
-    SpeakerSt sp;                                                                      // Speaker::new(BASE_SR); set_character(c)
-    sp.character = 1.0; sp.ts = 0.0;
-    sp.hpf.s1 = sp.hpf.s2 = sp.lpf.s1 = sp.lpf.s2 = 0.0;
-    speaker_update(sp, K->sr);
-    speaker_set_character(sp, speaker, K->sr);
+    SpeakerSt sp = speaker_fresh(K->sr, speaker);                                      // at BASE_SR
     for (long long i = 0; i < n; ++i) {
         const double amp = mode == CALIB_OUT_FULL ? power_amp(x[i] * volume * volume) : x[i];
         y[i] = speaker_process(sp, amp, K->spk_thermal_alpha) * 7.498942093324558;        // tables::POST_SPEAKER_GAIN

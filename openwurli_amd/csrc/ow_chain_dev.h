@@ -980,6 +980,15 @@ OW_DEV void speaker_set_character(SpeakerSt& s, double ch, double sr) {  // spea
     const double c = clampd(ch, 0.0, 1.0);
     if (fabs(c - s.character) > 0.002) { s.character = c; speaker_update(s, sr); }
 }
+// Speaker::new(sr); set_character(character): what every job-path chain starts from (main.rs:483-484)
+__device__ __forceinline__ SpeakerSt speaker_fresh(double sr, double character) {
+    SpeakerSt s;
+    s.character = 1.0; s.ts = 0.0;
+    s.hpf.s1 = s.hpf.s2 = s.lpf.s1 = s.lpf.s2 = 0.0;
+    speaker_update(s, sr);
+    speaker_set_character(s, character, sr);
+    return s;
+}
 OW_DEV double speaker_process(SpeakerSt& s, double input, double thermal_alpha) {  // speaker.rs:105-132
     const double x2 = input * input;
     const double x3 = x2 * input;

@@ -471,11 +471,7 @@ __global__ __launch_bounds__(320) void k_job_chain_row(const OwConsts* __restric
     const OwJobDev jd = jobs[valid ? j : n_jobs - 1];
     const double sr = K->sr;
     double da[3] = {0, 0, 0}, db[3] = {0, 0, 0}, dd = 0.0;
-    SpeakerSt sp;
-    sp.character = 1.0; sp.ts = 0.0;                         // Speaker::new(sr); set_character(c)  (main.rs:483-484)
-    sp.hpf.s1 = sp.hpf.s2 = sp.lpf.s1 = sp.lpf.s2 = 0.0;
-    speaker_update(sp, sr);
-    speaker_set_character(sp, jd.speaker, sr);
+    SpeakerSt sp = speaker_fresh(sr, jd.speaker);
     const double vol2_a = jd.volume;
     for (long long c = 0; c <= n_chunks; ++c) {
         if (c >= 1) {

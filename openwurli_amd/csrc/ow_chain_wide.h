@@ -178,11 +178,7 @@ __global__ __launch_bounds__(64) void k_job_chain_wide(const OwConsts* __restric
         return res;
     };
     double ua[3] = {0, 0, 0}, ub[3] = {0, 0, 0}, da[3] = {0, 0, 0}, db[3] = {0, 0, 0}, dd = 0.0;
-    SpeakerSt sp;                                      // Speaker::new(sr); set_character(c)  (main.rs:483-484)
-    sp.character = 1.0; sp.ts = 0.0;
-    sp.hpf.s1 = sp.hpf.s2 = sp.lpf.s1 = sp.lpf.s2 = 0.0;
-    speaker_update(sp, sr);
-    speaker_set_character(sp, jd.speaker, sr);
+    SpeakerSt sp = speaker_fresh(sr, jd.speaker);
     const double vol2_a = jd.volume;
 
     for (long long base = 0; base < n; base += OW_WCHUNK) {
@@ -590,6 +586,8 @@ __global__ __launch_bounds__(128) void k_job_chain_fused(const OwConsts* __restr
         const double r_new = fmax(jd.r_ldr, 1000.0);
         if (fabs(r_new - r_ldr) > 0.01) { r_ldr = r_new; g_ldr = 1.0 / r_new; }
     } else {
+        // speaker_fresh(sr, jd.speaker), typed out: assigned to the lane's `sp` from this branch, the helper's copy changes the kernel's
+        // register assignment
         sp.character = 1.0; sp.ts = 0.0;                         // Speaker::new(sr); set_character(c)  (main.rs:483-484)
         sp.hpf.s1 = sp.hpf.s2 = sp.lpf.s1 = sp.lpf.s2 = 0.0;
         speaker_update(sp, sr);

@@ -165,11 +165,7 @@ __global__ __launch_bounds__(64) void k_job_chain(const OwConsts* __restrict__ K
         return res;
     };
     double ua[3] = {0, 0, 0}, ub[3] = {0, 0, 0}, da[3] = {0, 0, 0}, db[3] = {0, 0, 0}, dd = 0.0;
-    SpeakerSt sp;                                      // Speaker::new(sr); set_character(c)  (main.rs:483-484)
-    sp.character = 1.0; sp.ts = 0.0;
-    sp.hpf.s1 = sp.hpf.s2 = sp.lpf.s1 = sp.lpf.s2 = 0.0;
-    speaker_update(sp, sr);
-    speaker_set_character(sp, jd.speaker, sr);
+    SpeakerSt sp = speaker_fresh(sr, jd.speaker);
     const double vol2_a = jd.volume;
 
     for (long long base = 0; base < n; base += OW_PCHUNK) {
@@ -221,11 +217,7 @@ __global__ __launch_bounds__(64) void k_job_speaker(const OwConsts* __restrict__
     const int j = blockIdx.x * 64 + threadIdx.x;
     if (j >= n_jobs) return;
     const OwJobDev jd = jobs[j];
-    SpeakerSt sp;
-    sp.character = 1.0; sp.ts = 0.0;
-    sp.hpf.s1 = sp.hpf.s2 = sp.lpf.s1 = sp.lpf.s2 = 0.0;
-    speaker_update(sp, K->sr);
-    speaker_set_character(sp, jd.speaker, K->sr);
+    SpeakerSt sp = speaker_fresh(K->sr, jd.speaker);
     const double* src = (jd.poweramp ? amp : att) + (size_t)j * stride;      // all three buffers share the row stride
     double* dst = out + (size_t)j * stride;
     for (long long i = 0; i < n; ++i) dst[i] = speaker_process(sp, src[i], K->spk_thermal_alpha) * 7.498942093324558;

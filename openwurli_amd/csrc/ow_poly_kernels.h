@@ -112,11 +112,7 @@ __global__ __launch_bounds__(64) void k_poly_chain(const OwConsts* __restrict__ 
         return r;
     };
     double ua[3] = {0, 0, 0}, ub[3] = {0, 0, 0}, da[3] = {0, 0, 0}, db[3] = {0, 0, 0}, dd = 0.0;
-    SpeakerSt sp;                                      // Speaker::new(BASE_SR); set_character(c)  (main.rs:1471-1472)
-    sp.character = 1.0; sp.ts = 0.0;
-    sp.hpf.s1 = sp.hpf.s2 = sp.lpf.s1 = sp.lpf.s2 = 0.0;
-    speaker_update(sp, sr);
-    speaker_set_character(sp, cd.speaker, sr);
+    SpeakerSt sp = speaker_fresh(sr, cd.speaker);      // at BASE_SR (main.rs:1471-1472)
     const double vol = cd.volume;
     const bool walker = valid && sl.k == 0 && role == 0;      // the chord's one lane that recombines its chains
     const int nn = cd.n_notes;

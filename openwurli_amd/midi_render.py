@@ -8,7 +8,7 @@ import numpy as np
 
 from .binding import OwError, OwMidiRenderCfg, OwMidiRenderStats, TIMED_EVENT_DTYPE, load_library, take_error
 
-BASE_SR = 44100.0        # main.rs:27
+from ._rust_text import BASE_SR  # noqa: F401
 NOTE_ON, NOTE_OFF, PEDAL = 0, 1, 2
 
 

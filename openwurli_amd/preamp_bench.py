@@ -14,7 +14,7 @@ import numpy as np
 
 from .binding import PBENCH_SAMPLES, OwError, OwPreampMeasureCfg, OwPreampMeasureRow, OwPreampPoint, load_library, take_error
 
-BASE_SR = 44100.0                                           # main.rs:27
+from ._rust_text import BASE_SR, _f  # noqa: F401
 PREAMP_LEGACY8, PREAMP_MELANGE12 = 0, 1
 R_NEW = 1_000_000.0                                         # the r_ldr DkPreamp::new() solves DC at (dk_preamp_legacy.rs:269-366)
 
@@ -130,13 +130,7 @@ def response_surface(freqs: Sequence[float], r_ldrs: Sequence[float], amplitude=
     return rows["gain_db"].reshape(len(r_ldrs), len(freqs))
 
 
-# ---- the reference's text (main.rs:192-368).  Rust's {:.N} rounds the exact binary value half to even, as Python's %-format does.
-def _f(x, spec):
-    if math.isnan(x):                                       # Rust prints NaN as "NaN" (and inf as "inf", as Python does)
-        return ("%" + spec.split(".")[0].lstrip("+") + "s") % "NaN"
-    return ("%" + spec) % x
-
-
+# ---- the reference's text (main.rs:192-368), numbers through _f
 def target_db(r_ldr: float) -> float:                       # main.rs:201
     return 6.0 if r_ldr > 500_000.0 else 12.1
 

@@ -16,7 +16,7 @@ import numpy as np
 
 from .binding import POLY_MAX_NOTES, WAV_ROUND, OwError, OwPolyCfg, OwPolyChord, OwPolyRow, load_library, take_error
 
-BASE_SR = 44100.0                                           # main.rs:27
+from ._rust_text import BASE_SR, _f, midi_note_name, samples, to_dbfs  # noqa: F401
 WIN_LO, WIN_HI = 8820, 88200                                # (0.2 * BASE_SR) / (2.0 * BASE_SR) as usize, main.rs:1516-1517
 DEFAULT_NOTES, DEFAULT_VELOCITIES = (38, 59, 62, 66), (45, 40, 40, 40)      # main.rs:1398-1399
 
@@ -45,11 +45,6 @@ def parse_csv_u8(text: str) -> list:
     return out
 
 
-def midi_note_name(note: int) -> str:
-    """main.rs:666-673."""
-    return "%s%d" % (("C", "C#", "D", "D#", "E", "F", "F#", "G", "G#", "A", "A#", "B")[note % 12], note // 12 - 1)
-
-
 def make_chord(notes, velocities=(), volume=0.60, speaker=1.0, ldr=1_000_000.0, no_poweramp=False) -> np.ndarray:
     """One CHORD_DTYPE record; the velocities are padded to the notes by the command's rule."""
     notes = [int(x) for x in notes]
@@ -69,12 +64,6 @@ def make_chords(chords) -> np.ndarray:
         return np.ascontiguousarray(chords).ravel()
     out = [make_chord(**c) if isinstance(c, dict) else (c.reshape(1) if isinstance(c, (np.ndarray, np.void)) else make_chord(*c)) for c in chords]
     return np.concatenate(out) if out else np.zeros(0, dtype=CHORD_DTYPE)
-
-
-def samples(duration: float) -> int:
-    """(duration * BASE_SR) as usize."""
-    x = float(duration) * BASE_SR
-    return int(x) if x > 0 else 0
 
 
 def run_chords(chords, duration=3.0, device=0, final=False, separate_sum=False, residual=False, preamp_kind=0, power_amp_kind=0):
@@ -112,11 +101,6 @@ def default_output() -> str:
     return os.path.join(tempfile.gettempdir(), "preamp_render_poly.wav")
 
 
-def to_dbfs(val: float) -> float:
-    """main.rs:2241-2247."""
-    return 20.0 * math.log10(val) if val > 1e-15 else -120.0
-
-
 def verdict(ratio_db: float) -> str:
     """main.rs:1579-1587."""
     if ratio_db > 60.0:
@@ -126,13 +110,6 @@ def verdict(ratio_db: float) -> str:
     if ratio_db > 20.0:
         return "MARGINAL — intermod may be audible on revealing systems"
     return "DIRTY — intermod clearly audible"
-
-
-def _f(x, spec):
-    x = float(x)
-    if math.isnan(x):                                       # Rust prints NaN as "NaN" (and inf as "inf", as Python does)
-        return "NaN"
-    return ("%" + spec) % x
 
 
 def format_report(notes, velocities, duration, volume, speaker, row, output, residual_output=None) -> str:
