@@ -521,6 +521,113 @@ long long ow_centroid_track(const ow_centroid_job* jobs, size_t n_jobs, const ow
 long long ow_centroid_analyze(const double* signals, size_t n_rows, size_t stride, size_t len, size_t window_samples, size_t hop_samples,
                               size_t end_sample, int device, int signals_is_device, double* frames_out, size_t frames_stride);
 
+/* ---- note audits (`preamp-bench intermod-audit` and `overshoot`, tools/preamp-bench/src/main.rs:675-903, 2137-2247) ------------ */
+/* Both commands audit Voice::render_note(note, velocity / 127, duration, 44100) alone: one voice (MLP off, attack noise on, seed
+ * note * 2654435761, the note's own displacement scale; voice.rs:191-221), no preamp, no power amp, no speaker. */
+typedef struct ow_note_job {
+    uint8_t note;                    /* 33..96 */
+    uint8_t velocity;                /* 0..127 (velocity / 127.0); `intermod-audit` itself renders at 1.0 = 127 */
+    uint8_t reserved[6];
+} ow_note_job;
+
+/* tables::intermod_risk (tables.rs:675-801): how close the ratio of each mode 2..7 lies to an integer harmonic. */
+typedef struct ow_intermod_product {
+    uint32_t mode;                   /* 2..7 (1-indexed, as the command prints it) */
+    uint32_t nearest_integer;        /* ratio.round() as u32 */
+    double mode_ratio;
+    double fractional_offset;        /* |ratio - nearest| */
+    double beat_hz;                  /* fractional_offset * fundamental_hz */
+    double effective_amplitude;      /* BASE_MODE_AMPLITUDES x spatial coupling x dwell attenuation at ff */
+    double perceptual_weight;        /* perceptual_beat_weight(beat_hz) */
+    double risk_score;               /* effective_amplitude * perceptual_weight */
+} ow_intermod_product;
+typedef struct ow_intermod_report {
+    uint8_t midi;
+    uint8_t reserved[7];
+    double fundamental_hz, mu;
+    ow_intermod_product products[6];
+    double max_risk, total_risk;
+} ow_intermod_report;
+/* Host only (no device): the report of any MIDI byte, as the reference's function accepts any.  Returns 0, <0 on a null `out`. */
+int ow_intermod_risk(uint8_t midi, ow_intermod_report* out);
+
+/* dft_magnitude (:893-903) of the window [start, end) of every row: signals f64 [n_rows][stride] (a device pointer if signals_is_device
+ * != 0), freqs host f64 [n_rows][n_probes], mags_out host f64 [n_rows][n_probes].  The phase index counts from the window start.  A NaN
+ * entry of freqs means "no probe": its output is 0.0 and costs nothing.  Returns 0, <0 on error: end > stride, end <= start, a null
+ * pointer, a sample rate that is not a finite positive number, a device error. */
+int ow_dft_magnitudes(const double* signals, size_t n_rows, size_t stride, size_t start, size_t end, double sample_rate, const double* freqs,
+                      size_t n_probes, int device, int signals_is_device, double* mags_out);
+
+#define OW_INTERMOD_MAX_PROBES 75    /* 32 harmonics + 31 midpoints + 6 x (mode frequency, nearest harmonic) */
+/* Host only: the probe frequencies of the render analysis for one note, in the order the analysis sums them: harmonics n * f0 for
+ * n = 1..=H, H = min(floor(22050 / f0), 32), stopping at the first >= 22050; midpoints (n + 0.5) * f0 for n in 1..H with the same stop;
+ * then, for each product with risk_score >= 0.001, mode_ratio * f0 and nearest_integer * f0.  freqs_out: [OW_INTERMOD_MAX_PROBES] (the
+ * rest is left untouched).  Returns the probe count, <0 on error (a null pointer, a note outside 33..96). */
+int ow_intermod_probes(uint8_t midi, double* freqs_out, uint32_t* n_harmonics_out, uint32_t* n_midpoints_out);
+
+typedef struct ow_intermod_cfg {
+    uint32_t struct_size;  /* = sizeof(ow_intermod_cfg) of the caller's header */
+    uint32_t job_size;     /* = sizeof(ow_note_job) of the caller's header (the stride of `jobs`) */
+    double duration_s;     /* --duration (default 3.0) */
+    int device;
+    int reserved;
+} ow_intermod_cfg;
+enum { OW_INTERMOD_DIRTY = 0, OW_INTERMOD_MARGINAL = 1, OW_INTERMOD_OK = 2, OW_INTERMOD_CLEAN = 3 };
+typedef struct ow_intermod_detail {  /* one line of "Per-product detail" (:869-886) */
+    uint32_t mode, nearest_integer;
+    double intermod_freq, nearest_freq;       /* mode_ratio * f0, nearest_integer * f0 */
+    double intermod_mag, nearest_mag;         /* dft_magnitude of the window at them */
+    double ratio_db;                          /* 20 log10(intermod_mag / nearest_mag), 0.0 when nearest_mag <= 1e-15 */
+    double risk_score;
+    uint8_t listed;                           /* risk_score >= 0.001: the command lists it; the magnitudes are 0 otherwise */
+    uint8_t reserved[7];
+} ow_intermod_detail;
+typedef struct ow_intermod_row {
+    uint8_t midi, velocity;
+    uint8_t too_short;                        /* end <= start: "(signal too short)", every figure below is 0 */
+    uint8_t verdict;                          /* OW_INTERMOD_*: ratio_db > 40 CLEAN, > 30 OK, > 20 MARGINAL, else DIRTY */
+    uint32_t n_harmonics, n_midpoints;        /* probes that entered the two energy sums */
+    uint32_t window_start, window_end;        /* (0.5 * 44100) as usize, (2.0 * 44100).min(len) as usize */
+    uint32_t reserved;
+    double fundamental_hz;
+    double harmonic_energy, midpoint_energy;  /* sums of mag^2 in probe order */
+    double h_db, m_db, ratio_db;              /* 10 log10 of the energies (-120.0 when not > 0), h_db - m_db */
+    ow_intermod_detail products[6];           /* always filled: only the command's text applies its `ratio_db <= 30.0` rule */
+} ow_intermod_row;
+/* The render analysis of cmd_intermod_audit (:822-888) for n_jobs (note, velocity) jobs at once.  rows_out: [n_jobs].  audio_out: NULL,
+ * or host f64 [n_jobs][audio_stride >= (duration_s * 44100) as usize] receiving the voice rows; asking for it changes no number.  The
+ * rows stay in HBM between render and analysis; large grids run in chunks of a fixed device-memory budget (OW_NOTE_AUDIT_CHUNK=<jobs>
+ * caps a chunk; tests use it).  A job's numbers do not depend on the other jobs of the call or on the chunking.  When the window is
+ * empty (duration <= 0.5 s) every row says too_short and, unless audio_out is given, no device is needed.  n_jobs == 0 returns the
+ * sample count and touches nothing.
+ * Returns the samples per job, <0 on error.  Refused before any device work (ow_last_error says why): "ABI mismatch", a note outside
+ * 33..96, a velocity above 127, a duration giving 2^31 samples or more, a short audio_stride, null arguments. */
+long long ow_intermod_audit(const ow_note_job* jobs, size_t n_jobs, const ow_intermod_cfg* cfg, ow_intermod_row* rows_out, double* audio_out,
+                            size_t audio_stride);
+
+typedef struct ow_overshoot_cfg {
+    uint32_t struct_size;  /* = sizeof(ow_overshoot_cfg) of the caller's header */
+    uint32_t job_size;     /* = sizeof(ow_note_job) of the caller's header (the stride of `jobs`) */
+    double duration_s;     /* the command's constant 2.0 (:2151), a parameter here */
+    int device;
+    int reserved;
+} ow_overshoot_cfg;
+/* cmd_overshoot's figures (:2167-2221).  Window edges are (t * 44100.0) as usize, clamped to the length as the command's slices and
+ * rms_window (:2231-2239) clamp them; an empty window gives peak 0.0 / RMS 0.0. */
+typedef struct ow_overshoot_row {
+    uint8_t note, velocity;
+    uint8_t reserved[6];
+    double peak_0_10, peak_0_50;              /* max |x| over 0-10 ms, 0-50 ms */
+    double rms_100_200, rms_1000_1500;        /* sqrt(sum x^2 / (e - s)) */
+    double overshoot_db;                      /* 20 log10(peak_0_10 / rms_100_200), NaN unless rms_100_200 > 1e-15 */
+    double bark_decay_db;                     /* 20 log10(peak_0_50 / rms_1000_1500), NaN unless rms_1000_1500 > 1e-15 */
+    double pk_dbfs, rms1_dbfs, rms2_dbfs;     /* to_dbfs (:2241-2247) of peak_0_10, rms_100_200, rms_1000_1500: -120.0 at <= 1e-15 */
+} ow_overshoot_row;
+/* cmd_overshoot for n_jobs (note, velocity) jobs at once; rows_out, audio_out, chunking, independence, the return value and the refusals
+ * as for ow_intermod_audit.  A duration of 0 samples needs no device. */
+long long ow_overshoot(const ow_note_job* jobs, size_t n_jobs, const ow_overshoot_cfg* cfg, ow_overshoot_row* rows_out, double* audio_out,
+                       size_t audio_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,18 @@ int ow_test_engine_read_preamp_state(ow_engine*, int shadow, double* out14);
 /* Plain device-to-host copy, for reading a block that ow_pool_render(pool, NULL, ...) left in HBM (ow_pool_device_output). */
 int ow_test_device_read(void* dst_host, const void* src_device, size_t bytes, int device);
 
+/* k_window_stats (the analysis kernel of ow_overshoot) on given host rows: signals f64 [n_rows][stride]; up to four windows [starts[k],
+ * ends[k]) with ends[k] <= stride, kinds[k] 0 = max |x| (NaN samples ignored, an empty window gives 0), 1 = sum of squares; out host f64
+ * [n_rows][n_windows].  Returns 0, <0 on error. */
+int ow_debug_window_stats(const double* signals, size_t n_rows, size_t stride, const uint32_t* starts, const uint32_t* ends, const uint32_t* kinds,
+                          size_t n_windows, int device, double* out);
+/* The voices' per-note table as the device builds it (tables.rs:804-830 and the note-only scalars of Voice::note_on): out host f64
+ * [OW_TEST_NOTE_TABLE_FIELDS][64], field-major, note index = midi - 33.  Fields: 0 detuned f0, 1..7 mode ratios, 8..14 base amplitude x
+ * spatial coupling, 15..21 decay rates, 22..28 amplitude offsets, 29 displacement scale, 30 velocity exponent, 31 f0, 32 register trim,
+ * 33 voicing.  Returns 0, <0 on error. */
+#define OW_TEST_NOTE_TABLE_FIELDS 34
+int ow_debug_note_table(double* out, int device);
+
 /* Fast paths of the melange preamp's literal rebuild the host found usable at chain rate `rate` (host only): bit 0 = leading block
  * replayed once per rate, bit 1 = the LU factors have the compiled-in sparsity pattern of the column-streamed kernel.  <0 on error. */
 int ow_test_host_melange_paths(double rate);

@@ -9,6 +9,17 @@ def midi_note_name(note: int) -> str:
     return "%s%d" % (("C", "C#", "D", "D#", "E", "F", "F#", "G", "G#", "A", "A#", "B")[note % 12], note // 12 - 1)
 
 
+def parse_csv_u8(text: str) -> list:
+    """parse_csv_list::<u8> (main.rs:907-910): comma-separated, trimmed, items that are no u8 are dropped."""
+    out = []
+    for item in text.split(","):
+        item = item.strip()
+        digits = item[1:] if item[:1] == "+" else item
+        if digits.isascii() and digits.isdigit() and int(digits) <= 255:
+            out.append(int(digits))
+    return out
+
+
 def as_usize(x: float) -> int:
     """Rust's `f64 as usize`: NaN and negatives give 0."""
     return int(x) if x > 0 and math.isfinite(x) else 0

@@ -171,6 +171,59 @@ class OwCentroidRow(C.Structure):
                 ("attack_status", C.c_uint8), ("sustain_status", C.c_uint8), ("drift_status", C.c_uint8), ("reserved", C.c_uint8 * 3)]
 
 
+INTERMOD_MAX_PROBES = 75                                    # include/openwurli_hip.h OW_INTERMOD_MAX_PROBES
+INTERMOD_DIRTY, INTERMOD_MARGINAL, INTERMOD_OK, INTERMOD_CLEAN = 0, 1, 2, 3      # ow_intermod_row.verdict
+
+
+class OwNoteJob(C.Structure):
+    _fields_ = [("note", C.c_uint8), ("velocity", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+
+
+class OwIntermodProduct(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("nearest_integer", C.c_uint32), ("mode_ratio", C.c_double), ("fractional_offset", C.c_double),
+                ("beat_hz", C.c_double), ("effective_amplitude", C.c_double), ("perceptual_weight", C.c_double), ("risk_score", C.c_double)]
+
+
+class OwIntermodReport(C.Structure):
+    _fields_ = [("midi", C.c_uint8), ("reserved", C.c_uint8 * 7), ("fundamental_hz", C.c_double), ("mu", C.c_double),
+                ("products", OwIntermodProduct * 6), ("max_risk", C.c_double), ("total_risk", C.c_double)]
+
+
+class OwIntermodCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("job_size", C.c_uint32), ("duration_s", C.c_double), ("device", C.c_int), ("reserved", C.c_int)]
+
+    def __init__(self, duration_s=3.0, device=0):
+        super().__init__(C.sizeof(OwIntermodCfg), C.sizeof(OwNoteJob), duration_s, device, 0)
+
+
+class OwIntermodDetail(C.Structure):
+    _fields_ = [("mode", C.c_uint32), ("nearest_integer", C.c_uint32), ("intermod_freq", C.c_double), ("nearest_freq", C.c_double),
+                ("intermod_mag", C.c_double), ("nearest_mag", C.c_double), ("ratio_db", C.c_double), ("risk_score", C.c_double),
+                ("listed", C.c_uint8), ("reserved", C.c_uint8 * 7)]
+
+
+class OwIntermodRow(C.Structure):
+    _fields_ = [("midi", C.c_uint8), ("velocity", C.c_uint8), ("too_short", C.c_uint8), ("verdict", C.c_uint8), ("n_harmonics", C.c_uint32),
+                ("n_midpoints", C.c_uint32), ("window_start", C.c_uint32), ("window_end", C.c_uint32), ("reserved", C.c_uint32), ("fundamental_hz", C.c_double),
+                ("harmonic_energy", C.c_double), ("midpoint_energy", C.c_double), ("h_db", C.c_double), ("m_db", C.c_double),
+                ("ratio_db", C.c_double), ("products", OwIntermodDetail * 6)]
+
+
+class OwOvershootCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("job_size", C.c_uint32), ("duration_s", C.c_double), ("device", C.c_int), ("reserved", C.c_int)]
+
+    def __init__(self, duration_s=2.0, device=0):
+        super().__init__(C.sizeof(OwOvershootCfg), C.sizeof(OwNoteJob), duration_s, device, 0)
+
+
+OVERSHOOT_ROW_FIELDS = ("peak_0_10", "peak_0_50", "rms_100_200", "rms_1000_1500", "overshoot_db", "bark_decay_db", "pk_dbfs", "rms1_dbfs",
+                        "rms2_dbfs")
+
+
+class OwOvershootRow(C.Structure):
+    _fields_ = [("note", C.c_uint8), ("velocity", C.c_uint8), ("reserved", C.c_uint8 * 6)] + [(f, C.c_double) for f in OVERSHOOT_ROW_FIELDS]
+
+
 # every symbol include/openwurli_hip.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 class OwSegment(C.Structure):
@@ -256,6 +309,11 @@ SYMBOLS = {
     "ow_centroid_frame_count": (C.c_longlong, [C.POINTER(OwCentroidCfg)]),
     "ow_centroid_track": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwCentroidCfg), _VP, _VP, C.c_size_t, _VP, C.c_size_t]),
     "ow_centroid_analyze": (C.c_longlong, [_VP, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _VP, C.c_size_t]),
+    "ow_intermod_risk": (C.c_int, [C.c_uint8, C.POINTER(OwIntermodReport)]),
+    "ow_dft_magnitudes": (C.c_int, [_VP, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, _VP, C.c_size_t, C.c_int, C.c_int, _VP]),
+    "ow_intermod_probes": (C.c_int, [C.c_uint8, _VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ow_intermod_audit": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwIntermodCfg), _VP, _VP, C.c_size_t]),
+    "ow_overshoot": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwOvershootCfg), _VP, _VP, C.c_size_t]),
 }
 
 
@@ -288,6 +346,8 @@ TEST_SYMBOLS = {
     "ow_test_pool_trajectory_state": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     "ow_test_host_melange_paths": (C.c_int, [C.c_double]),
     "ow_test_device_read": (C.c_int, [_VP, _VP, C.c_size_t, C.c_int]),
+    "ow_debug_window_stats": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, _VP, _VP, C.c_size_t, C.c_int, _VP]),
+    "ow_debug_note_table": (C.c_int, [_VP, C.c_int]),
     "ow_test_engine_poke_voice": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_double]),
     "ow_test_engine_poke_preamp_node": (C.c_int, [_VP, C.c_int, C.c_int, C.c_double]),
     "ow_test_engine_read_preamp_state": (C.c_int, [_VP, C.c_int, _VP]),

@@ -38,6 +38,7 @@
 #include "ow_pbench_kernels.h"
 #include "ow_poly_kernels.h"
 #include "ow_centroid_kernels.h"
+#include "ow_note_audit_kernels.h"
 #include "ow_midi_kernels.h"
 #include "ow_chain_wide.h"
 #include "ow_chain_stream.h"
@@ -68,3 +69,4 @@ using owdev::OwEngineOut;
 #include "host/api_preamp_measure.inc"  // C-ABI: `preamp-bench gain` / `sweep` / `harmonics` / `tremolo-sweep` (the preamp measurements)
 #include "host/api_render_poly.inc"     // C-ABI: `preamp-bench render-poly` (chord intermodulation, many chords per call)
 #include "host/api_centroid.inc"        // C-ABI: `preamp-bench centroid-track` (spectral centroid over time, many notes per call)
+#include "host/api_note_audit.inc"      // C-ABI: `preamp-bench intermod-audit` / `overshoot` (the note audits, many notes per call)

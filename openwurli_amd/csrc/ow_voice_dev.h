@@ -18,6 +18,9 @@
 namespace owdev {
 
 #define OW_DEV __device__ __forceinline__
+// the note-only table maths below also runs on the host (ow_intermod_risk): one copy for both sides
+#define OW_HD __host__ __device__ __forceinline__
+#define OW_HDI __host__ __device__ inline
 
 // IEEE-754 f64 division for the hot loops.  hipcc expands a / b into v_div_scale x2, v_rcp, 2 Newton steps, q = a*y, residual,
 // v_div_fmas, v_div_fixup (11 instructions).  The two v_div_scale only pre-scale operands whose exponents are extreme (denormal
@@ -78,7 +81,7 @@ OW_DEV double ow_div_const(double a, const double b, const double y) {
 }
 #define OW_DIV_C(a, B) ow_div_const((a), (B), 1.0 / (B))
 #define OW_JITTER_DIV 2147483647.5            // reed.rs:267-272
-OW_DEV double clampd(double x, double lo, double hi) {  // Rust f64::clamp (NaN propagates)
+OW_HD double clampd(double x, double lo, double hi) {  // Rust f64::clamp (NaN propagates)
     return x < lo ? lo : (x > hi ? hi : x);
 }
 OW_DEV uint64_t dbits(double x) { return (uint64_t)__double_as_longlong(x); }
@@ -93,7 +96,7 @@ OW_DEV uint64_t sat_u64(double x) {  // Rust `as u64`
 // ------------------------------------------------------------------ per-note table
 // One thread per MIDI note 33..96.  tables.rs:804-830 + variation.rs:26-38 + the note-only
 // scalars Voice::note_on needs (ds, velocity exponent, trim, voicing).
-OW_DEV double tip_mass_ratio(double m) {  // tables.rs:51-77
+OW_HD double tip_mass_ratio(double m) {  // tables.rs:51-77
     const double ax[5] = {33.0, 52.0, 62.0, 74.0, 96.0};
     const double ay[5] = {0.10, 0.00, 0.00, 0.02, 0.01};
     if (m <= ax[0]) return ay[0];
@@ -111,28 +114,39 @@ OW_DEV double tip_mass_ratio(double m) {  // tables.rs:51-77
     return r;
 }
 
-__device__ const double EIG_MU[8] = {0.00, 0.01, 0.05, 0.10, 0.15, 0.20, 0.30, 0.50};
-__device__ const double EIG_BETA[8][7] = {  // tables.rs:91-124
-    {1.8751, 4.6941, 7.8548, 10.9955, 14.1372, 17.2788, 20.4204}, {1.8584, 4.6849, 7.8504, 10.9930, 14.1356, 17.2776, 20.4195},
-    {1.7920, 4.6477, 7.8316, 10.9830, 14.1288, 17.2726, 20.4158}, {1.7227, 4.6024, 7.8077, 10.9700, 14.1198, 17.2660, 20.4110},
-    {1.6625, 4.5618, 7.7859, 10.9580, 14.1114, 17.2598, 20.4065}, {1.6097, 4.5254, 7.7659, 10.9470, 14.1036, 17.2540, 20.4023},
-    {1.5201, 4.4620, 7.7310, 10.9280, 14.0894, 17.2434, 20.3946}, {1.3853, 4.3601, 7.6745, 10.8970, 14.0650, 17.2252, 20.3814},
-};
-__device__ inline void eigenvalues(double mu, double out[7]) {  // tables.rs:85-143
+#define OW_EIG_MU_VALUES {0.00, 0.01, 0.05, 0.10, 0.15, 0.20, 0.30, 0.50}
+#define OW_EIG_BETA_VALUES {  /* tables.rs:91-124 */ \
+    {1.8751, 4.6941, 7.8548, 10.9955, 14.1372, 17.2788, 20.4204}, {1.8584, 4.6849, 7.8504, 10.9930, 14.1356, 17.2776, 20.4195}, \
+    {1.7920, 4.6477, 7.8316, 10.9830, 14.1288, 17.2726, 20.4158}, {1.7227, 4.6024, 7.8077, 10.9700, 14.1198, 17.2660, 20.4110}, \
+    {1.6625, 4.5618, 7.7859, 10.9580, 14.1114, 17.2598, 20.4065}, {1.6097, 4.5254, 7.7659, 10.9470, 14.1036, 17.2540, 20.4023}, \
+    {1.5201, 4.4620, 7.7310, 10.9280, 14.0894, 17.2434, 20.3946}, {1.3853, 4.3601, 7.6745, 10.8970, 14.0650, 17.2252, 20.3814}, \
+}
+__device__ const double EIG_MU[8] = OW_EIG_MU_VALUES;
+__device__ const double EIG_BETA[8][7] = OW_EIG_BETA_VALUES;
+#ifdef __HIP_DEVICE_COMPILE__
+#define OW_EIG(table) table
+#else
+namespace host_tables {          // the host pass cannot read a __device__ array: the same values, once more in host memory
+const double EIG_MU[8] = OW_EIG_MU_VALUES;
+const double EIG_BETA[8][7] = OW_EIG_BETA_VALUES;
+}
+#define OW_EIG(table) host_tables::table
+#endif
+OW_HDI void eigenvalues(double mu, double out[7]) {  // tables.rs:85-143
     const double mc = clampd(mu, 0.0, 0.50);
     int lo = 0;
     for (int i = 7; i >= 0; --i)
-        if (EIG_MU[i] <= mc) { lo = i; break; }
+        if (OW_EIG(EIG_MU)[i] <= mc) { lo = i; break; }
     const int hi = lo + 1 < 7 ? lo + 1 : 7;
-    const double t = (EIG_MU[hi] > EIG_MU[lo]) ? (mc - EIG_MU[lo]) / (EIG_MU[hi] - EIG_MU[lo]) : 0.0;
-    for (int i = 0; i < 7; ++i) out[i] = EIG_BETA[lo][i] + t * (EIG_BETA[hi][i] - EIG_BETA[lo][i]);
+    const double t = (OW_EIG(EIG_MU)[hi] > OW_EIG(EIG_MU)[lo]) ? (mc - OW_EIG(EIG_MU)[lo]) / (OW_EIG(EIG_MU)[hi] - OW_EIG(EIG_MU)[lo]) : 0.0;
+    for (int i = 0; i < 7; ++i) out[i] = OW_EIG(EIG_BETA)[lo][i] + t * (OW_EIG(EIG_BETA)[hi][i] - OW_EIG(EIG_BETA)[lo][i]);
 }
-__device__ inline double mode_shape(double beta, double xi) {  // tables.rs:295-299
+OW_HDI double mode_shape(double beta, double xi) {  // tables.rs:295-299
     const double sigma = (cosh(beta) + cos(beta)) / (sinh(beta) + sin(beta));
     const double bx = beta * xi;
     return cosh(bx) - cos(bx) - sigma * (sinh(bx) - sin(bx));
 }
-__device__ inline double reed_length_mm(double midi) {  // tables.rs:161-169
+OW_HDI double reed_length_mm(double midi) {  // tables.rs:161-169
     const double n = clampd(midi - 32.0, 1.0, 64.0);
     const double inches = (n <= 20.0) ? 3.0 - n / 20.0 : 2.0 - (n - 20.0) / 44.0;
     return inches * 25.4;
@@ -165,25 +179,15 @@ __device__ inline double register_trim_db(double m) {  // tables.rs:443-481
     return 0.0;
 }
 
-__global__ void k_note_table(double* __restrict__ nt) {
-    const int ni = threadIdx.x;
-    if (ni >= 64) return;
-    const int midi = OW_MIDI_LO + ni;
-    const double m = (double)midi;
-    const double f0 = 440.0 * pow(2.0, (m - 69.0) / 12.0);                        // tables.rs:37-39
-    const double detune = 1.0 + (hash01((uint32_t)midi, 0xDEADu) * 2.0 - 1.0) * 0.00173;  // variation.rs:26-29
-    nt[NT_F0 * 64 + ni] = f0;
-    nt[NT_F0D * 64 + ni] = f0 * detune;
-    const double mu = tip_mass_ratio(m);
-    double betas[7], ratios[7];
-    eigenvalues(mu, betas);
+OW_HDI double midi_to_freq(double m) { return 440.0 * pow(2.0, (m - 69.0) / 12.0); }            // tables.rs:37-39
+OW_HDI void mode_ratios(const double betas[7], double ratios[7]) {                            // tables.rs:149-153
     const double b1sq = betas[0] * betas[0];
-    for (int i = 0; i < 7; ++i) ratios[i] = (betas[i] * betas[i]) / b1sq;          // tables.rs:149-153
-    const double base_decay = fmax(0.005 * pow(f0, 1.22), 3.0);                    // tables.rs:391-396
-    // spatial pickup coupling, 32-interval Simpson (tables.rs:324-370)
-    const double ell = clampd(6.0 / reed_length_mm(m), 0.0, 1.0);
+    for (int i = 0; i < 7; ++i) ratios[i] = (betas[i] * betas[i]) / b1sq;
+}
+// spatial pickup coupling before its normalisation to mode 1, 32-interval Simpson (tables.rs:324-362)
+OW_HDI void spatial_coupling_raw(const double betas[7], double reed_len_mm, double kraw[7]) {
+    const double ell = clampd(6.0 / reed_len_mm, 0.0, 1.0);
     const double xi_start = 1.0 - ell;
-    double kraw[7];
     for (int mode = 0; mode < 7; ++mode) {
         const double beta = betas[mode];
         const double tip = mode_shape(beta, 1.0);
@@ -197,10 +201,30 @@ __global__ void k_note_table(double* __restrict__ nt) {
         const double integral = sum * h / 3.0;
         kraw[mode] = clampd(fabs(integral / (ell * tip)), 0.0, 1.0);
     }
-    const double base_amp[7] = {1.0, 0.005, 0.0035, 0.0018, 0.0011, 0.0007, 0.0005};  // tables.rs:33-34
+}
+OW_HDI double spatial_coupling_norm(double kraw_i, double k1) { return (k1 > 1e-30) ? clampd(kraw_i / k1, 0.0, 1.0) : 1.0; }   // tables.rs:364-369
+#define OW_BASE_MODE_AMPLITUDES {1.0, 0.005, 0.0035, 0.0018, 0.0011, 0.0007, 0.0005}     /* tables.rs:33-34 */
+
+__global__ void k_note_table(double* __restrict__ nt) {
+    const int ni = threadIdx.x;
+    if (ni >= 64) return;
+    const int midi = OW_MIDI_LO + ni;
+    const double m = (double)midi;
+    const double f0 = midi_to_freq(m);
+    const double detune = 1.0 + (hash01((uint32_t)midi, 0xDEADu) * 2.0 - 1.0) * 0.00173;  // variation.rs:26-29
+    nt[NT_F0 * 64 + ni] = f0;
+    nt[NT_F0D * 64 + ni] = f0 * detune;
+    const double mu = tip_mass_ratio(m);
+    double betas[7], ratios[7];
+    eigenvalues(mu, betas);
+    mode_ratios(betas, ratios);
+    const double base_decay = fmax(0.005 * pow(f0, 1.22), 3.0);                    // tables.rs:391-396
+    double kraw[7];
+    spatial_coupling_raw(betas, reed_length_mm(m), kraw);
+    const double base_amp[7] = OW_BASE_MODE_AMPLITUDES;
     const double k1 = kraw[0];
     for (int i = 0; i < 7; ++i) {
-        const double kap = (k1 > 1e-30) ? clampd(kraw[i] / k1, 0.0, 1.0) : 1.0;
+        const double kap = spatial_coupling_norm(kraw[i], k1);
         nt[(NT_RATIO + i) * 64 + ni] = ratios[i];
         nt[(NT_AMP + i) * 64 + ni] = base_amp[i] * kap;
         nt[(NT_DECAY + i) * 64 + ni] = base_decay * ratios[i] * ratios[i];           // tables.rs:418-422

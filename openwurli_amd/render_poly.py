@@ -16,7 +16,7 @@ import numpy as np
 
 from .binding import POLY_MAX_NOTES, WAV_ROUND, OwError, OwPolyCfg, OwPolyChord, OwPolyRow, load_library, take_error
 
-from ._rust_text import BASE_SR, _f, midi_note_name, samples, to_dbfs  # noqa: F401
+from ._rust_text import BASE_SR, _f, midi_note_name, parse_csv_u8, samples, to_dbfs  # noqa: F401
 WIN_LO, WIN_HI = 8820, 88200                                # (0.2 * BASE_SR) / (2.0 * BASE_SR) as usize, main.rs:1516-1517
 DEFAULT_NOTES, DEFAULT_VELOCITIES = (38, 59, 62, 66), (45, 40, 40, 40)      # main.rs:1398-1399
 
@@ -32,17 +32,6 @@ def pad_velocities(notes: Sequence[int], velocities_raw: Sequence[int]) -> list:
     """main.rs:1410-1420: one velocity per note; missing ones repeat the last given, 80 when none was given; extra ones are dropped."""
     raw = list(velocities_raw)
     return [raw[i] if i < len(raw) else (raw[-1] if raw else 80) for i in range(len(notes))]
-
-
-def parse_csv_u8(text: str) -> list:
-    """parse_csv_list::<u8> (main.rs:907-910): comma-separated, trimmed, items that are no u8 are dropped."""
-    out = []
-    for item in text.split(","):
-        item = item.strip()
-        digits = item[1:] if item[:1] == "+" else item
-        if digits.isascii() and digits.isdigit() and int(digits) <= 255:
-            out.append(int(digits))
-    return out
 
 
 def make_chord(notes, velocities=(), volume=0.60, speaker=1.0, ldr=1_000_000.0, no_poweramp=False) -> np.ndarray:
