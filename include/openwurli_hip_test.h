@@ -69,6 +69,17 @@ int ow_debug_dk_step(int form, double rate, const double* states_in, const doubl
  * first fifteen of ow_debug_trem_trajectory's state rows); out: [n] = the step's return value, v[OUT]; info: [n] = the step's increment of
  * the backward-Euler fallback counter.  Cases fill the wavefronts in order; n need not fill the last one.  Returns 0, <0 on error. */
 int ow_debug_trem_step(int form, double rate, const double* states_in, size_t n, double* states_out, double* out, unsigned long long* info, int device);
+/* ONE step of the melange 12-node preamp solver (set_runtime_R; process_sample, gen_preamp.rs:1973-1984, 3399-3663) on n independent
+ * cases at chain rate `rate`, through one of its device forms: 0 = mel_process, the rank-one form with MelMats in LDS (k_preamp_mel,
+ * k_mel_settle); 1 / 2 = mel_process_lit after the fast leading-block / the generic rebuild (k_preamp_mel_lit); 3 / 4 = mel_process_col,
+ * fast / generic (k_preamp_mel_col); 5 / 6 = mel_eng_sample, fast / generic (k_preamp_mel_eng).  The production device functions with
+ * the production constants of that rate; no noise; mel_set_r(r_ldr) runs before the step.  states_in / states_out: [n][21] = v[12],
+ * i_nl_prev[3], i_nl_prev_prev[3], input_prev, pot, be_cooldown (as a double); input, r_ldr, out: [n]; info: [n][2] = the step's
+ * increments of the backward-Euler fallback and NaN-reset counters.  Forms 1-6 take case 2k as an engine's main state and case 2k+1 as
+ * its shadow and build the matrices for the main's pot; forms 5 / 6 also give the shadow the main's resistance and input 0, so a shadow
+ * case is expected to carry those.  n need not fill the last wavefront or pair.  Returns 0, <0 on error. */
+int ow_debug_mel_step(int form, double rate, const double* states_in, const double* input, const double* r_ldr, size_t n, double* states_out, double* out,
+                      unsigned* info, int device);
 
 /* ---- tremolo phase groups -------------------------------------------------------------------- */
 /* Engines whose tremolo oscillators are bit-identical share one oscillator (a fresh pool is one group).  This hook cuts the pool into

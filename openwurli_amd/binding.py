@@ -331,6 +331,7 @@ TEST_SYMBOLS = {
     "ow_debug_unary": (C.c_int, [C.c_int, _VP, C.c_size_t, _VP, _VP, C.c_int]),
     "ow_debug_dk_step": (C.c_int, [C.c_int, C.c_double, _VP, _VP, _VP, _VP, C.c_size_t, _VP, _VP, C.c_int]),
     "ow_debug_trem_step": (C.c_int, [C.c_int, C.c_double, _VP, C.c_size_t, _VP, _VP, _VP, C.c_int]),
+    "ow_debug_mel_step": (C.c_int, [C.c_int, C.c_double, _VP, _VP, _VP, C.c_size_t, _VP, _VP, _VP, C.c_int]),
     "ow_test_inject_render_faults": (None, [_VP, C.c_int]),
     "ow_debug_power_amp": (C.c_int, [C.c_double, _VP, C.c_size_t, C.c_size_t, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int]),
     "ow_test_pool_enable_power_amp_tap": (C.c_int, [_VP]),

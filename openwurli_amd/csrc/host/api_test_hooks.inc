@@ -576,4 +576,58 @@ int ow_debug_trem_step(int form, double rate, const double* states_in, size_t n,
         return 0;
     } catch (const std::exception& ex) { (void)hipGetLastError(); set_err(std::string("ow_debug_trem_step: ") + ex.what()); return -1; }
 }
+int ow_debug_mel_step(int form, double rate, const double* states_in, const double* input, const double* r_ldr, size_t n, double* states_out, double* out,
+                      unsigned* info, int device) {
+    try {
+        if (!states_in || !input || !r_ldr || !states_out || !out || !info || form < 0 || form > 6 || !(rate > 0.0)) throw std::runtime_error("bad argument");
+        if (n == 0) return 0;
+        if (n > (size_t)1 << 22) throw std::runtime_error("too many cases");
+        HIP_OK(hipSetDevice(device));
+        std::unique_ptr<OwConsts> hc(new OwConsts());
+        // build_consts takes the HOST rate; a host rate >= 88.2 kHz runs the chain at that rate without oversampling (engine.rs:195)
+        owhip::build_consts(*hc, rate < 88200.0 ? rate * 0.5 : rate, OW_PREAMP_MELANGE12);
+        if (hc->os_sr != rate) throw std::runtime_error("rate is not reachable as a chain rate");
+        // the pool launches a form only where the host found its fast path usable (host_pool.inc)
+        if (form == 1 && !hc->ml_ok) throw std::runtime_error("the leading block cannot be replayed at this rate");
+        if (form >= 3 && !hc->ml_sparse_ok) throw std::runtime_error("the factors do not have the compiled-in pattern at this rate");
+        const size_t pairs = (n + 1) / 2;
+        const size_t per_block = form == 0 ? 64 : (form <= 4 ? 32 : 64);          // cases | pairs | pairs | engines of one wavefront
+        const size_t units = form == 0 ? n : pairs;
+        const size_t blocks = (units + per_block - 1) / per_block;
+        // the generic rebuilds' workspace, as pool_create sizes d_mel_lu: lane-minor columns with 32 spare pairs for lanes without an
+        // engine (col / eng), one [12][12][32] slab per workgroup (lit)
+        const size_t lu_ld = 2 * (pairs + 32);
+        const size_t lu_doubles = 144 * std::max<size_t>(lu_ld, 32 * (blocks + 1));
+        DevMem dK, dS, dX, dR, dSo, dO, dI, dLu;
+        dK.alloc(sizeof(OwConsts)); dS.alloc(sizeof(double) * 21 * n); dX.alloc(sizeof(double) * n); dR.alloc(sizeof(double) * n);
+        dSo.alloc(sizeof(double) * 21 * n); dO.alloc(sizeof(double) * n); dI.alloc(sizeof(unsigned) * 2 * n); dLu.alloc(sizeof(double) * lu_doubles);
+        HIP_OK(hipMemcpy(dK.p, hc.get(), sizeof(OwConsts), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dS.p, states_in, sizeof(double) * 21 * n, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dX.p, input, sizeof(double) * n, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dR.p, r_ldr, sizeof(double) * n, hipMemcpyHostToDevice));
+        HIP_OK(hipMemset(dSo.p, 0, sizeof(double) * 21 * n));
+        HIP_OK(hipMemset(dO.p, 0, sizeof(double) * n));
+        HIP_OK(hipMemset(dI.p, 0, sizeof(unsigned) * 2 * n));
+        HIP_OK(hipMemset(dLu.p, 0, sizeof(double) * lu_doubles));
+        const dim3 grid((unsigned)blocks), block(64);
+        const OwConsts* K = dK.as<OwConsts>();
+#define OW_MEL_STEP_LAUNCH(F) owdev::k_debug_mel_step<F><<<grid, block>>>(K, dS.as<double>(), dX.as<double>(), dR.as<double>(), (int)n, dSo.as<double>(), \
+                                                                         dO.as<double>(), dI.as<unsigned>(), dLu.as<double>(), lu_ld)
+        switch (form) {
+            case 0: OW_MEL_STEP_LAUNCH(owdev::MSF_RANK1); break;
+            case 1: OW_MEL_STEP_LAUNCH(owdev::MSF_LIT_FAST); break;
+            case 2: OW_MEL_STEP_LAUNCH(owdev::MSF_LIT_GENERIC); break;
+            case 3: OW_MEL_STEP_LAUNCH(owdev::MSF_COL_FAST); break;
+            case 4: OW_MEL_STEP_LAUNCH(owdev::MSF_COL_GENERIC); break;
+            case 5: OW_MEL_STEP_LAUNCH(owdev::MSF_ENG_FAST); break;
+            default: OW_MEL_STEP_LAUNCH(owdev::MSF_ENG_GENERIC); break;
+        }
+#undef OW_MEL_STEP_LAUNCH
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpy(states_out, dSo.p, sizeof(double) * 21 * n, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(out, dO.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(info, dI.p, sizeof(unsigned) * 2 * n, hipMemcpyDeviceToHost));
+        return 0;
+    } catch (const std::exception& ex) { (void)hipGetLastError(); set_err(std::string("ow_debug_mel_step: ") + ex.what()); return -1; }
+}
 }  // extern "C"

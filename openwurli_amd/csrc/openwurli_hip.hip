@@ -33,6 +33,7 @@
 #include "ow_chain_row.h"
 #include "ow_dk_step_debug.h"
 #include "ow_trem_step_debug.h"
+#include "ow_mel_step_debug.h"
 #include "ow_audit.h"
 #include "ow_calib_kernels.h"
 #include "ow_pbench_kernels.h"

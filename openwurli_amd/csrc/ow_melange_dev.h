@@ -349,7 +349,9 @@ __device__ inline double mel_process(MelSt& st, double input_in, const MelMats* 
     double wr = 0.0;
 #pragma unroll
     for (int j = 0; j < 12; ++j) wr += M->w[j] * rhs[j];
-    const double cwr = c * wr;
+    // (at the nominal pot c is exactly 0 and S(R) is S0: the correction vanishes there whatever wr is -- 0 * inf would make every node NaN
+    // where the reference has overflowed voltages that its ringing test still sees)
+    const double cwr = c == 0.0 ? 0.0 : c * wr;
     double v_pred[12];
     {   // column sweep: every row still accumulates its terms in j order (same sums), but only the twelve running sums are live
         // while a column of the matrix streams through, instead of whole rows of it waiting in registers
@@ -372,7 +374,7 @@ __device__ inline double mel_process(MelSt& st, double input_in, const MelMats* 
         for (int j = 0; j < 3; ++j) kk[i][j] = M->k0[i][j] - c * M->nvu[i] * M->wn[j];
     double i_nl[3];
     uint32_t last_it = mel_solve_nl(p, kk, st.ip, st.ipp, i_nl);
-    const double cwi = c * (M->wn[0] * i_nl[0] + M->wn[1] * i_nl[1] + M->wn[2] * i_nl[2]);
+    const double cwi = c == 0.0 ? 0.0 : c * (M->wn[0] * i_nl[0] + M->wn[1] * i_nl[1] + M->wn[2] * i_nl[2]);
     double vn[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) {                                     // v = v_pred + S(R) N_i i_nl

@@ -28,6 +28,63 @@ __device__ inline void mel_eng_step(const OwConsts* __restrict__ K, const MelCol
     mel_col_fold_sni<COL>(b, sni);
 }
 
+// One sample of one engine: process_sample of the main state (input in_main) and of the shadow state (input 0) with the matrices of
+// `pot` built once.  The per-sample body of k_preamp_mel_eng, as a function so that tests/test_gpu_mel_step.py can take single steps
+// through it (ow_mel_step_debug.h); o receives the two return values.
+__device__ inline void mel_eng_sample(MelSt (&st)[2], double in_main, double pot, double alpha, const OwConsts* __restrict__ K, double* __restrict__ sni,
+                                      bool force_generic, double* __restrict__ lu, size_t lu_ld, const double* nzp, int nz_stride, double (&o)[2]) {
+    // ---- (1) per state: clamp, flush, cooldown, build_rhs
+    double rhs[2][12], input[2];
+    bool force_be[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+        mel_col_pre(st[s], s ? 0.0 : in_main, pot, alpha, K, s ? nullptr : nzp, nz_stride, rhs[s], input[s], force_be[s]);
+    // ---- (2) once per engine: factor, unit columns, fold into both states' sums
+    double vp[2][12];
+    {
+        double acc_a[12], acc_b[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) { acc_a[i] = 0.0; acc_b[i] = 0.0; }
+        bool fast = !force_generic;
+        if (fast) {
+            MelColT T;
+            fast = mel_col_factor(K, pot, alpha, T);
+            if (__builtin_expect(fast, 1)) {
+                mel_eng_step<0>(K, T, rhs[0][0], rhs[1][0], acc_a, acc_b, sni);
+                mel_eng_step<1>(K, T, rhs[0][1], rhs[1][1], acc_a, acc_b, sni);
+                mel_eng_step<2>(K, T, rhs[0][2], rhs[1][2], acc_a, acc_b, sni);
+                mel_eng_step<3>(K, T, rhs[0][3], rhs[1][3], acc_a, acc_b, sni);
+                mel_eng_step<4>(K, T, rhs[0][4], rhs[1][4], acc_a, acc_b, sni);
+                mel_eng_step<5>(K, T, rhs[0][5], rhs[1][5], acc_a, acc_b, sni);
+                mel_eng_step<6>(K, T, rhs[0][6], rhs[1][6], acc_a, acc_b, sni);
+                mel_eng_step<7>(K, T, rhs[0][7], rhs[1][7], acc_a, acc_b, sni);
+                mel_eng_step<8>(K, T, rhs[0][8], rhs[1][8], acc_a, acc_b, sni);
+                mel_eng_step<9>(K, T, rhs[0][9], rhs[1][9], acc_a, acc_b, sni);
+                mel_eng_step<10>(K, T, rhs[0][10], rhs[1][10], acc_a, acc_b, sni);
+                mel_eng_step<11>(K, T, rhs[0][11], rhs[1][11], acc_a, acc_b, sni);
+            }
+        }
+        if (__builtin_expect(!fast, 0)) {
+            MelColGen g;
+            for (int i = 0; i < 12; ++i) g.rhs[i] = rhs[1][i];
+            mel_col_generic(pot, alpha, lu, lu_ld, &g);
+            for (int i = 0; i < 12; ++i) acc_b[i] = g.acc[i];
+            for (int i = 0; i < 12; ++i) g.rhs[i] = rhs[0][i];
+            mel_col_generic(pot, alpha, lu, lu_ld, &g);
+            for (int i = 0; i < 12; ++i) acc_a[i] = g.acc[i];
+            for (int k = 0; k < 3; ++k) for (int i = 0; i < 12; ++i) MCOL_SNI(k, i) = g.sni[k][i];
+        }
+#pragma unroll
+        for (int i = 0; i < 12; ++i) { vp[0][i] = acc_a[i]; vp[1][i] = acc_b[i]; }
+    }
+    double kk[3][3];
+    mel_col_kernel(sni, kk);
+    // ---- (3) per state: Newton, update, guards
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+        o[s] = mel_col_post(st[s], input[s], force_be[s], vp[s], kk, sni, s ? nullptr : nzp, nz_stride);
+}
+
 __global__ __launch_bounds__(64, 2) void k_preamp_mel_eng(const OwConsts* __restrict__ K, double* __restrict__ cs,
                                                           const double* __restrict__ settled, const OwEngineArgs* __restrict__ args,
                                                           const OwEngineOut* __restrict__ eout, const double* __restrict__ sum, const OwTremSrc tsrc,
@@ -108,57 +165,8 @@ __global__ __launch_bounds__(64, 2) void k_preamp_mel_eng(const OwConsts* __rest
                 nzp = nzcol;
             }
             const uint32_t nan_before = st[0].nan_resets;
-            // ---- (1) per state: clamp, flush, cooldown, build_rhs
-            double rhs[2][12], input[2];
-            bool force_be[2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-                mel_col_pre(st[s], s ? 0.0 : in[j], pot, alpha, K, s ? nullptr : nzp, I, rhs[s], input[s], force_be[s]);
-            // ---- (2) once per engine: factor, unit columns, fold into both states' sums
-            double vp[2][12];
-            {
-                double acc_a[12], acc_b[12];
-#pragma unroll
-                for (int i = 0; i < 12; ++i) { acc_a[i] = 0.0; acc_b[i] = 0.0; }
-                bool fast = !force_generic;
-                if (fast) {
-                    MelColT T;
-                    fast = mel_col_factor(K, pot, alpha, T);
-                    if (__builtin_expect(fast, 1)) {
-                        mel_eng_step<0>(K, T, rhs[0][0], rhs[1][0], acc_a, acc_b, sni);
-                        mel_eng_step<1>(K, T, rhs[0][1], rhs[1][1], acc_a, acc_b, sni);
-                        mel_eng_step<2>(K, T, rhs[0][2], rhs[1][2], acc_a, acc_b, sni);
-                        mel_eng_step<3>(K, T, rhs[0][3], rhs[1][3], acc_a, acc_b, sni);
-                        mel_eng_step<4>(K, T, rhs[0][4], rhs[1][4], acc_a, acc_b, sni);
-                        mel_eng_step<5>(K, T, rhs[0][5], rhs[1][5], acc_a, acc_b, sni);
-                        mel_eng_step<6>(K, T, rhs[0][6], rhs[1][6], acc_a, acc_b, sni);
-                        mel_eng_step<7>(K, T, rhs[0][7], rhs[1][7], acc_a, acc_b, sni);
-                        mel_eng_step<8>(K, T, rhs[0][8], rhs[1][8], acc_a, acc_b, sni);
-                        mel_eng_step<9>(K, T, rhs[0][9], rhs[1][9], acc_a, acc_b, sni);
-                        mel_eng_step<10>(K, T, rhs[0][10], rhs[1][10], acc_a, acc_b, sni);
-                        mel_eng_step<11>(K, T, rhs[0][11], rhs[1][11], acc_a, acc_b, sni);
-                    }
-                }
-                if (__builtin_expect(!fast, 0)) {
-                    MelColGen g;
-                    for (int i = 0; i < 12; ++i) g.rhs[i] = rhs[1][i];
-                    mel_col_generic(pot, alpha, lu, lu_ld, &g);
-                    for (int i = 0; i < 12; ++i) acc_b[i] = g.acc[i];
-                    for (int i = 0; i < 12; ++i) g.rhs[i] = rhs[0][i];
-                    mel_col_generic(pot, alpha, lu, lu_ld, &g);
-                    for (int i = 0; i < 12; ++i) acc_a[i] = g.acc[i];
-                    for (int k = 0; k < 3; ++k) for (int i = 0; i < 12; ++i) MCOL_SNI(k, i) = g.sni[k][i];
-                }
-#pragma unroll
-                for (int i = 0; i < 12; ++i) { vp[0][i] = acc_a[i]; vp[1][i] = acc_b[i]; }
-            }
-            double kk[3][3];
-            mel_col_kernel(sni, kk);
-            // ---- (3) per state: Newton, update, guards
             double o[2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-                o[s] = mel_col_post(st[s], input[s], force_be[s], vp[s], kk, sni, s ? nullptr : nzp, I);
+            mel_eng_sample(st, in[j], pot, alpha, K, sni, force_generic, lu, lu_ld, nzp, I, o);
             if (nz_mine && st[0].nan_resets != nan_before) nz_clear_lag(nzcol, I);
             double result = o[0] - o[1];
             if (!isfinite(result)) {

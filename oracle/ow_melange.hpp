@@ -23,6 +23,30 @@ namespace owo {
 
 constexpr int PN = 12, PM = 3;
 
+// Test instrumentation of MelState::process_sample (owo_melange_step_cases): how one step went.  Plain counters; observes, changes nothing.
+struct MelStepTrace {
+    int trap_sweeps = 0;    // sweeps the trapezoidal solve ran (1 = converged at sweep 0; 265 with nr_failed = exhausted)
+    int be_taken = 0;       // the backward-Euler fallback ran
+    int be_sweeps = 0;      // ... and its solve ran this many sweeps
+    int nr_failed = 0;      // the trapezoidal solve used up all 265 sweeps
+    int ringing = 0;        // a node of the trapezoidal result lay beyond 55 V
+    int forced = 0;         // the cooldown forced the fallback
+    int lim_sweeps = 0, cap_sweeps = 0, singular_sweeps = 0;   // sweeps (of either solve) that pnjlim shortened / the 0.1 A cap cut / with a singular Jacobian
+    int damped = 0, nan_reset = 0, rebuilt = 0;                // the voltage-damp net fired / the step ended in the reset / process_sample rebuilt the matrices
+    int thr_sweeps = 0;     // sweeps in which a port's step exceeded the limiter's 1e-4 V threshold
+    int be_failed = 0;      // the fallback's solve used up all 265 sweeps too
+    int sweeps = 0;         // (scratch: sweeps of the solve that is running)
+};
+inline MelStepTrace*& mel_trace() { static thread_local MelStepTrace* t = nullptr; return t; }
+// Test instrumentation: rebuild_matrices sees the resistance moved by this many doubles (what a resistance computed by another libm is).
+// Thread-local, 0 unless owo_melange_step_cases sets it for the duration of its call.
+inline int& mel_r_ulp() { static thread_local int k = 0; return k; }
+inline double mel_r_moved(double r) {
+    for (int k = mel_r_ulp(); k > 0; --k) r = std::nextafter(r, INFINITY);
+    for (int k = mel_r_ulp(); k < 0; ++k) r = std::nextafter(r, -INFINITY);
+    return r;
+}
+
 struct MelState {
     double v_prev[PN], i_nl_prev[PM], i_nl_prev_prev[PM], input_prev;
     uint32_t last_nr_iterations, be_cooldown;
@@ -200,7 +224,7 @@ struct MelState {
         const double alpha = 2.0 * (current_sample_rate * 1.0);
         double g_eff[PN][PN];
         std::memcpy(g_eff, PRE_G, sizeof g_eff);
-        g_eff[6][6] += 1.0 / pot_0_resistance - PRE_POT_0_G_NOM;
+        g_eff[6][6] += 1.0 / mel_r_moved(pot_0_resistance) - PRE_POT_0_G_NOM;
         double a[PN][PN], an[PN][PN];
         for (int i = 0; i < PN; ++i)
             for (int j = 0; j < PN; ++j) {
@@ -230,7 +254,10 @@ struct MelState {
     // :3122-3357; kk/ = active kernel (K or K_be)
     void solve_nonlinear(const double p[PM], const double kk[PM][PM], double i_nl[PM]) {
         for (int i = 0; i < PM; ++i) i_nl[i] = 2.0 * i_nl_prev[i] - i_nl_prev_prev[i];
+        MelStepTrace* const tr = mel_trace();
+        if (tr) tr->sweeps = 0;
         for (int iter = 0; iter < 265; ++iter) {
+            if (tr) tr->sweeps += 1;
             const double v_d0 = p[0] + kk[0][0] * i_nl[0] + kk[0][1] * i_nl[1] + kk[0][2] * i_nl[2];
             const double v_d1 = p[1] + kk[1][0] * i_nl[0] + kk[1][1] * i_nl[1] + kk[1][2] * i_nl[2];
             const double v_d2 = p[2] + kk[2][0] * i_nl[0] + kk[2][1] * i_nl[1] + kk[2][2] * i_nl[2];
@@ -289,8 +316,10 @@ struct MelState {
                 const double vcr[3] = {PRE_DEVICE_0_VCRIT, PRE_DEVICE_1_VCRIT, PRE_DEVICE_2_VCRIT};
                 double alpha[3] = {1.0, 1.0, 1.0};
                 bool any_limited = false;
+                bool tr_thr = false;
                 for (int q = 0; q < 3; ++q) {
                     if (std::fabs(dv[q]) > 1e-4) {
+                        tr_thr = true;
                         const double v_lim = pnjlim(vd[q] + dv[q], vd[q], vts[q], vcr[q]);
                         const double ratio = std::fmax((v_lim - vd[q]) / dv[q], 0.01);
                         if (ratio < alpha[q]) { alpha[q] = ratio; if (ratio < 1.0) any_limited = true; }
@@ -299,6 +328,7 @@ struct MelState {
                 double alpha_scalar = std::fmin(alpha[0], std::fmin(alpha[1], alpha[2]));
                 if (alpha_scalar < 1.0) any_limited = true;
                 const double max_di = std::fmax(std::fmax(std::fabs(delta0), std::fabs(delta1)), std::fabs(delta2));
+                if (tr) { tr->thr_sweeps += tr_thr; tr->lim_sweeps += any_limited; tr->cap_sweeps += (max_di * alpha_scalar > 0.1); }
                 if (max_di * alpha_scalar > 0.1) alpha_scalar = std::fmin(std::fmax(0.1 / max_di, 0.01), alpha_scalar);
                 i_nl[0] -= alpha_scalar * delta0;
                 i_nl[1] -= alpha_scalar * delta1;
@@ -319,6 +349,7 @@ struct MelState {
                 }
                 if (conv) { last_nr_iterations = (uint32_t)iter; return; }
             } else {
+                if (tr) tr->singular_sweeps += 1;
                 const double ff[3] = {f0, f1, f2};
                 for (int q = 0; q < 3; ++q) {
                     const double cl = std::fmax(std::fabs(i_nl[q]) * 0.1, 0.01);
@@ -332,7 +363,8 @@ struct MelState {
 
     double process_sample(double input_in) {  // :3399-3663
         const double input = std::isfinite(input_in) ? rclamp(input_in, -100.0, 100.0) : 0.0;
-        if (matrices_dirty) { rebuild_matrices(); matrices_dirty = false; }
+        MelStepTrace* const tr = mel_trace();
+        if (matrices_dirty) { rebuild_matrices(); matrices_dirty = false; if (tr) tr->rebuilt = 1; }
         for (int i = 0; i < PN; ++i) v_prev[i] = v_prev[i] + 1e-25 - 1e-25;
         for (int i = 0; i < PM; ++i) i_nl_prev[i] = i_nl_prev[i] + 1e-25 - 1e-25;
         const bool force_be = be_cooldown > 0;
@@ -389,6 +421,7 @@ struct MelState {
         const double p[PM] = {-v_pred[2], v_pred[2] - v_pred[5], v_pred[4] - v_pred[8]};
         double i_nl[PM];
         solve_nonlinear(p, k, i_nl);
+        if (tr) tr->trap_sweeps = tr->sweeps;
         double vn[PN];
         for (int i = 0; i < PN; ++i) {
             vn[i] = v_pred[i];
@@ -397,7 +430,9 @@ struct MelState {
         const bool nr_failed = last_nr_iterations >= 265u;
         bool ringing = false;
         for (int i = 0; i < 11; ++i) if (std::fabs(vn[i]) > 55.0) ringing = true;
+        if (tr) { tr->nr_failed = nr_failed; tr->ringing = ringing; tr->forced = force_be; }
         if (nr_failed || ringing || force_be) {
+            if (tr) tr->be_taken = 1;
             if (nr_failed) diag_nr_max_iter_count += 1;
             if (ringing || nr_failed) be_cooldown = 64;
             diag_be_fallback_count += 1;
@@ -424,6 +459,7 @@ struct MelState {
                 p_be[i] = sum;
             }
             solve_nonlinear(p_be, k_be, i_nl);
+            if (tr) { tr->be_sweeps = tr->sweeps; tr->be_failed = last_nr_iterations >= 265u; }
             for (int i = 0; i < PN; ++i) {
                 vn[i] = v_pred_be[i];
                 for (int j = 0; j < PM; ++j) vn[i] += s_ni_be[i][j] * i_nl[j];
@@ -437,6 +473,7 @@ struct MelState {
             const double damp_thresh = std::fma(max_dc, 0.05, 2.0);      // the path's one explicit mul_add (:3592)
             if (max_delta > damp_thresh) {
                 diag_voltage_damp_count += 1;
+                if (tr) tr->damped = 1;
                 const double damp = std::fmax(damp_thresh / max_delta, 0.01);
                 for (int i = 0; i < PN; ++i) vn[i] = v_prev[i] + damp * (vn[i] - v_prev[i]);
                 for (int i = 0; i < PM; ++i) i_nl[i] = i_nl_prev[i] + damp * (i_nl[i] - i_nl_prev[i]);
@@ -452,6 +489,7 @@ struct MelState {
             be_cooldown = 0;
             noise_clear_lag();                                              // :3625-3627 (RNG state preserved)
             diag_nan_reset_count += 1;
+            if (tr) tr->nan_reset = 1;
             return rclamp(PRE_DC_OP[10] * 1.0, -10.0, 10.0);
         }
         for (int i = 0; i < PN; ++i) v_prev[i] = vn[i];

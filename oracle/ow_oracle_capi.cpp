@@ -480,6 +480,82 @@ void owo_melange_run(double sr, const double* x, const double* r, double* y, siz
     }
     delete p;
 }
+// One solver state of that preamp run on as a recurrence, for harvesting states: init_state(rate) (the settled state, matrices of that
+// rate), then per step set_runtime_r_ldr(r[k]) (null: untouched) and process_sample(x[k]) (null: 0).  Stores the state row [21] in front of
+// every `every`-th step (before its set_runtime_r_ldr) into states_out [(n + every - 1) / every][21] and every step's return value into
+// y (nullable).
+static void mel_row_out(const MelState& s, double* o) {
+    for (int i = 0; i < PN; ++i) o[i] = s.v_prev[i];
+    for (int i = 0; i < PM; ++i) { o[12 + i] = s.i_nl_prev[i]; o[15 + i] = s.i_nl_prev_prev[i]; }
+    o[18] = s.input_prev; o[19] = s.pot_0_resistance; o[20] = (double)s.be_cooldown;
+}
+void owo_melange_harvest(double rate, const double* x, const double* r, size_t n, size_t every, double* states_out, double* y) {
+    MelState* s = new MelState(MelangePreamp::init_state(rate));
+    for (size_t k = 0; k < n; ++k) {
+        if (k % every == 0) mel_row_out(*s, states_out + 21 * (k / every));
+        if (r) s->set_runtime_r_ldr(r[k]);
+        const double o = s->process_sample(x ? x[k] : 0.0);
+        if (y) y[k] = o;
+    }
+    delete s;
+}
+// MelState::process_sample as a pure function of n independent cases at chain rate `rate` (tests/mel_step_cases.py).  A state row [21] is
+// v_prev[12], i_nl_prev[3], i_nl_prev_prev[3], input_prev, pot, be_cooldown (as a double).  Per case: a state at `rate` holding the row,
+// its trapezoidal matrices in sync with the row's pot -- the baked tables at the codegen rate and the nominal pot, as set_sample_rate
+// leaves them, rebuild_matrices otherwise --, noise off; then set_runtime_r_ldr(r_ldr[k]) and ONE process_sample(input[k]).
+// states_out [n][21], out [n] = the step's return value, info [n][14] (MelStepTrace): sweeps of the trapezoidal solve, fallback taken, its
+// sweeps, nr_failed, ringing, forced by the cooldown, sweeps shortened by pnjlim, sweeps cut by the 0.1 A cap, singular sweeps, damped,
+// NaN reset, matrices rebuilt by process_sample, sweeps with a port step above the limiter's 1e-4 V threshold, the fallback's solve
+// exhausted.  log_ulp: pnjlim's logarithm moved by that many doubles (trem_log_ulp: pnjlim is shared text); r_ulp: every rebuild sees
+// the clamped resistance moved by that many doubles.  Both for the duration of this call only.
+static void melange_step_cases(double rate, const double* states, const double* input, const double* r_ldr, size_t n, int log_ulp, int r_ulp,
+                               bool never_baked, double* states_out, double* out, int* info) {
+    MelState* base = new MelState();
+    base->init_default();
+    MelState* c = new MelState();
+    trem_log_ulp() = log_ulp;
+    mel_r_ulp() = r_ulp;
+    const bool codegen = std::fabs(rate - PRE_SAMPLE_RATE) < 0.5;
+    for (size_t k = 0; k < n; ++k) {
+        const double* s = states + 21 * k;
+        *c = *base;
+        c->current_sample_rate = rate;
+        for (int i = 0; i < PN; ++i) c->v_prev[i] = s[i];
+        for (int i = 0; i < PM; ++i) { c->i_nl_prev[i] = s[12 + i]; c->i_nl_prev_prev[i] = s[15 + i]; }
+        c->input_prev = s[18];
+        c->pot_0_resistance = s[19];
+        c->be_cooldown = (uint32_t)s[20];
+        if (never_baked || !(codegen && s[19] == 9.99999999999999854e4)) c->rebuild_matrices();
+        c->matrices_dirty = false;
+        c->set_runtime_r_ldr(r_ldr[k]);
+        MelStepTrace tr;
+        mel_trace() = &tr;
+        out[k] = c->process_sample(input[k]);
+        mel_trace() = nullptr;
+        mel_row_out(*c, states_out + 21 * k);
+        if (info) {
+            int* f = info + 14 * k;
+            f[0] = tr.trap_sweeps; f[1] = tr.be_taken; f[2] = tr.be_sweeps; f[3] = tr.nr_failed; f[4] = tr.ringing; f[5] = tr.forced;
+            f[6] = tr.lim_sweeps; f[7] = tr.cap_sweeps; f[8] = tr.singular_sweeps; f[9] = tr.damped; f[10] = tr.nan_reset; f[11] = tr.rebuilt;
+            f[12] = tr.thr_sweeps; f[13] = tr.be_failed;
+        }
+    }
+    trem_log_ulp() = 0;
+    mel_r_ulp() = 0;
+    delete c;
+    delete base;
+}
+void owo_melange_step_cases(double rate, const double* states, const double* input, const double* r_ldr, size_t n, int log_ulp, int r_ulp,
+                            double* states_out, double* out, int* info) {
+    melange_step_cases(rate, states, input, r_ldr, n, log_ulp, r_ulp, false, states_out, out, info);
+}
+// The same for a state whose resistance has moved before and come back: the reference never returns to the baked tables, so at the
+// codegen rate and the nominal pot the matrices are rebuild_matrices' too.  (Which of the two a state at the nominal pot runs on is
+// history that the state row does not carry; elsewhere the two entries are the same function.)
+void owo_melange_step_cases_rebuilt(double rate, const double* states, const double* input, const double* r_ldr, size_t n, double* states_out,
+                                    double* out, int* info) {
+    melange_step_cases(rate, states, input, r_ldr, n, 0, 0, true, states_out, out, info);
+}
 // same with the thermal noise of the main state on (seed != 0: deterministic), gain = thermal_gain
 void owo_melange_run_noise(double sr, const double* x, const double* r, double* y, size_t n, unsigned long long seed, double gain) {
     MelangePreamp* p = new MelangePreamp();

@@ -224,6 +224,43 @@ def trem_harvest(rate, n, every, state=None):
     return out
 
 
+MEL_INFO = ("trap_sweeps", "be_taken", "be_sweeps", "nr_failed", "ringing", "forced", "lim_sweeps", "cap_sweeps", "singular_sweeps", "damped", "nan_reset",
+            "rebuilt", "thr_sweeps", "be_failed")
+
+
+def melange_step_cases(rate, states, inputs, r_ldr, log_ulp=0, r_ulp=0, rebuilt=False):
+    """ONE MelState::process_sample (gen_preamp.rs:3399-3663) on each of n independent cases at chain rate `rate`: states [n][21] =
+    v_prev[12], i_nl_prev[3], i_nl_prev_prev[3], input_prev, pot, be_cooldown; matrices in sync with the row's pot; then
+    set_runtime_r_ldr(r_ldr[k]) and process_sample(inputs[k]).  Returns (states_out [n][21], out [n], info [n][14] in the order of
+    MEL_INFO).  log_ulp: pnjlim's logarithm moved by that many doubles; r_ulp: the resistance every rebuild sees moved by that many.
+    rebuilt: the state's resistance has moved before, so that at the codegen rate and the nominal pot it runs on rebuild_matrices'
+    tables, not the baked ones (the reference never returns to those; the state row does not carry that history)."""
+    st = np.ascontiguousarray(states, dtype=np.float64)
+    n = st.shape[0]
+    assert st.shape == (n, 21)
+    x = np.ascontiguousarray(inputs, dtype=np.float64); r = np.ascontiguousarray(r_ldr, dtype=np.float64)
+    assert x.shape == (n,) and r.shape == (n,)
+    so = np.zeros((n, 21)); out = np.zeros(n); info = np.zeros((n, 14), dtype=np.int32)
+    if rebuilt:
+        assert log_ulp == 0 and r_ulp == 0
+        lib().owo_melange_step_cases_rebuilt(C.c_double(rate), _p(st), _p(x), _p(r), C.c_size_t(n), _p(so), _p(out), _p(info))
+        return so, out, info
+    lib().owo_melange_step_cases(C.c_double(rate), _p(st), _p(x), _p(r), C.c_size_t(n), C.c_int(int(log_ulp)), C.c_int(int(r_ulp)), _p(so), _p(out), _p(info))
+    return so, out, info
+
+
+def melange_harvest(rate, n, every, x=None, r=None):
+    """(states [ceil(n / every)][21] in front of every `every`-th of n consecutive steps of one melange solver state from init_state(rate),
+    y [n] = every step's return value); per step set_runtime_r_ldr(r[k]) (None: untouched) and process_sample(x[k]) (None: 0)."""
+    n = int(n); every = int(every)
+    out = np.zeros(((n + every - 1) // every, 21)); y = np.zeros(n)
+    xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
+    rr = None if r is None else np.ascontiguousarray(r, dtype=np.float64)
+    assert (xx is None or xx.shape == (n,)) and (rr is None or rr.shape == (n,))
+    lib().owo_melange_harvest(C.c_double(rate), None if xx is None else _p(xx), None if rr is None else _p(rr), C.c_size_t(n), C.c_size_t(every), _p(out), _p(y))
+    return out, y
+
+
 def preamp_dc_nodes(rate, r_ldr):
     """The eight node voltages of the legacy preamp after set_ldr_resistance(r_ldr); reset() at chain rate `rate` (full_dc_solve at that R)."""
     v = np.zeros(8)
@@ -371,6 +408,15 @@ ABS_FLOOR_MELANGE_LIT_OUTPUT = 3.4e-8
 ABS_FLOOR_TREM_STEP_V = 0.0
 ABS_FLOOR_TREM_STEP_I = 6.5e-11
 
+# single steps of the melange preamp solver (tests/mel_step_cases.py, tests/test_gpu_mel_step.py): the twelve v rows and the six junction
+# currents are held to 1e-5 relative plus these.  Measured as the Twin-T's: the oracle's step against itself with pnjlim's logarithm one
+# double away and with the resistance every rebuild sees one double away, either way, on the finite cases that keep their fallback, reset
+# and cooldown decisions (all of them do) -- no row of any of the 40 872 finite cases moves by more than 1.9e-7 of its value (the worst:
+# a limited sweep count that changes by one at 88.2 kHz), so no row's tolerance is ever governed by a floor and 2.5 x 0 is 0
+# (tests/test_oracle_sensitivity.py::test_melange_step_floors).  The resistance knob moves nothing at all: 1/R enters
+# g_eff[6][6] = G[6][6] + (1/R - 1/R_nom), where one double of R (<= 1.1e-19 S at 1 kOhm) is below half an ulp of the sum.
+ABS_FLOOR_MELANGE_STEP_V = 0.0
+ABS_FLOOR_MELANGE_STEP_I = 0.0
 
 # Every absolute floor above with the one-ulp measurement that governs it (DESIGN.md section 2 carries the numbers).  The rule of the
 # table, asserted by tests/test_oracle_sensitivity.py on the CPU: floor <= 2.5 x (what the reference algorithm itself moves by, on the
@@ -382,6 +428,7 @@ FLOORS = {
     "ABS_FLOOR_SOAK_LFO": ABS_FLOOR_SOAK_LFO,
     "ABS_FLOOR_MELANGE_LIT_PREAMP": ABS_FLOOR_MELANGE_LIT_PREAMP, "ABS_FLOOR_MELANGE_LIT_OUTPUT": ABS_FLOOR_MELANGE_LIT_OUTPUT,
     "ABS_FLOOR_TREM_STEP_V": ABS_FLOOR_TREM_STEP_V, "ABS_FLOOR_TREM_STEP_I": ABS_FLOOR_TREM_STEP_I,
+    "ABS_FLOOR_MELANGE_STEP_V": ABS_FLOOR_MELANGE_STEP_V, "ABS_FLOOR_MELANGE_STEP_I": ABS_FLOOR_MELANGE_STEP_I,
 }
 FLOOR_RULE = 2.5
 

@@ -351,3 +351,31 @@ def test_trem_step_floors(oracle):
     assert worst_v == 0.0 and 1e-12 < worst_i < 1e-10, (worst_v, worst_i)
     assert oracle.ABS_FLOOR_TREM_STEP_V <= oracle.FLOOR_RULE * worst_v, worst_v
     assert oracle.ABS_FLOOR_TREM_STEP_I <= oracle.FLOOR_RULE * worst_i, worst_i
+
+
+def test_melange_step_floors(oracle):
+    """ABS_FLOOR_MELANGE_STEP_V / _I (single steps of the melange preamp solver, tests/mel_step_cases.py): the oracle's own movement with
+    pnjlim's logarithm one double away and with the resistance its rebuilds see one double away, either way, on the rows where a floor and
+    not the relative term would have to be the tolerance: the rows that move by more than 1e-5 of their value, in the finite cases that
+    keep their fallback, reset and cooldown decisions under the experiment.  There is none, in volts or amps: both floors are 0.  The
+    largest relative movement is printed; the resistance knob is checked to be what it looks like -- absorbed by the addition into
+    g_eff[6][6] -- and not a knob that is not connected."""
+    import mel_step_cases as mc
+    worst_v = worst_i = worst_rel = 0.0
+    moved = [0, 0, 0, 0]
+    for rate, ref in mc.references(oracle).items():
+        for k, (sp, op, fp) in enumerate(ref.perturbed[:4]):         # the four one-double moves (the fifth variant swaps whole tables)
+            keep = ref.finite & (fp[:, mc.DECISIONS] == ref.info[:, mc.DECISIONS]).all(axis=1)
+            assert keep[ref.finite].all()                            # no decision changes under any of them
+            d = np.abs(sp[keep][:, :18] - ref.states[keep][:, :18])
+            a = np.abs(ref.states[keep][:, :18])
+            moved[k] += int((d > 0).any(axis=1).sum())
+            worst_rel = max(worst_rel, float((d / np.maximum(a, 1e-300)).max()))
+            d = np.where(d > 1e-5 * a, d, 0.0)
+            worst_v, worst_i = max(worst_v, float(d[:, :12].max())), max(worst_i, float(d[:, 12:].max()))
+    print(f"\n[floor table] ABS_FLOOR_MELANGE_STEP_V {oracle.ABS_FLOOR_MELANGE_STEP_V:.1e}: one-ulp {worst_v:.2e}; ABS_FLOOR_MELANGE_STEP_I "
+          f"{oracle.ABS_FLOOR_MELANGE_STEP_I:.1e}: one-ulp {worst_i:.2e}; largest relative movement of a row {worst_rel:.2e}; cases moved by "
+          f"log +1 / -1, R +1 / -1: {moved}")
+    assert worst_v == 0.0 and worst_i == 0.0 and 1e-9 < worst_rel < 1e-5, (worst_v, worst_i, worst_rel)
+    assert moved[0] > 100 and moved[1] > 100 and moved[2] == 0 and moved[3] == 0, moved
+    assert oracle.ABS_FLOOR_MELANGE_STEP_V <= oracle.FLOOR_RULE * worst_v and oracle.ABS_FLOOR_MELANGE_STEP_I <= oracle.FLOOR_RULE * worst_i
