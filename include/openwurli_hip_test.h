@@ -192,6 +192,13 @@ int ow_test_pool_trajectory_state(const ow_pool*, uint64_t out[5]);
  * error would (exception inside the guarded region): the caller's block must come back as silence in every row, ow_last_error
  * must name the failure, and the renders after them must work again. */
 void ow_test_inject_render_faults(ow_pool*, int n_renders);
+/* The k-th acquisition (0-based) of a device buffer, pinned buffer, event or stream that the calling thread makes from now on throws
+ * a std::runtime_error naming this hook INSTEAD of calling HIP (a host exception: no device state is touched), then the hook disarms
+ * itself.  k < 0 disarms it.  Whatever entry point was running reports the error the way it reports a failed hipMalloc; nothing it
+ * had acquired up to there may stay behind, and the object it worked on must remain usable. */
+void ow_test_fail_acquire_after(int k);
+/* Device buffers, pinned buffers, events and streams the library owns right now, process-wide (pools, trajectory stores, running calls). */
+uint64_t ow_test_live_resources(void);
 
 #ifdef __cplusplus
 }

@@ -333,6 +333,8 @@ TEST_SYMBOLS = {
     "ow_debug_trem_step": (C.c_int, [C.c_int, C.c_double, _VP, C.c_size_t, _VP, _VP, _VP, C.c_int]),
     "ow_debug_mel_step": (C.c_int, [C.c_int, C.c_double, _VP, _VP, _VP, C.c_size_t, _VP, _VP, _VP, C.c_int]),
     "ow_test_inject_render_faults": (None, [_VP, C.c_int]),
+    "ow_test_fail_acquire_after": (None, [C.c_int]),
+    "ow_test_live_resources": (C.c_uint64, []),
     "ow_debug_power_amp": (C.c_int, [C.c_double, _VP, C.c_size_t, C.c_size_t, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int]),
     "ow_test_pool_enable_power_amp_tap": (C.c_int, [_VP]),
     "ow_test_pool_power_amp_passes": (C.c_int, [_VP, _VP, C.c_size_t]),

@@ -119,7 +119,7 @@ int ow_alias_audit_analyze(const double* signals, size_t n_signals, size_t strid
         if (n_signals == 0) return 0;
         HIP_OK(hipSetDevice(device));
         StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
+        so.create();
         DevMem d_sig;
         const double* src = signals;
         if (!signals_is_device) {
@@ -134,18 +134,18 @@ int ow_alias_audit_analyze(const double* signals, size_t n_signals, size_t strid
 
 int ow_alias_audit_run(const uint8_t* notes, const uint8_t* velocities, size_t n, int device, int preamp_kind,
                        ow_alias_audit_result* out, double* signals_out, size_t signals_stride) {
-    ow_pool* pool = nullptr;
     try {
         if (!notes || !velocities || !out) throw std::runtime_error("null argument");
         if (n == 0) return 0;
         const size_t total = (size_t)(AUDIT_SR * AUDIT_RENDER_S);   // :151
         if (signals_out && signals_stride < total) throw std::runtime_error("signals_stride shorter than the render");
         g_err.clear();
-        pool = ow_pool_new(AUDIT_SR, n, device, preamp_kind);       // WurliEngine::new(sr) per stimulus, :137
+        std::unique_ptr<ow_pool> owner(ow_pool_new(AUDIT_SR, n, device, preamp_kind));   // WurliEngine::new(sr) per stimulus, :137
+        ow_pool* pool = owner.get();
         if (!pool) throw std::runtime_error(g_err.empty() ? "pool creation failed" : g_err);
         ow_pool_ensure_buffer_capacity(pool, 1024);                 // :138
         for (size_t k = 0; k < n; ++k) {                            // :139-143
-            ow_engine* e = pool->engines[k];
+            ow_engine* e = pool->engines[k].get();
             ow_engine_set_volume(e, 0.5);
             ow_engine_set_tremolo_depth(e, 0.0);
             ow_engine_set_speaker_character(e, 0.0);
@@ -155,7 +155,7 @@ int ow_alias_audit_run(const uint8_t* notes, const uint8_t* velocities, size_t n
         for (int k = 0; k < 6; ++k) ow_pool_render(pool, nullptr, 0, 1024);   // smoother settle, :147-150
         std::vector<double> nominal(n);
         for (size_t k = 0; k < n; ++k) {
-            ow_engine_note_on(pool->engines[k], notes[k], (float)velocities[k] / 127.0f);   // :152
+            ow_engine_note_on(pool->engines[k].get(), notes[k], (float)velocities[k] / 127.0f);   // :152
             nominal[k] = 440.0 * std::pow(2.0, ((double)notes[k] - 69.0) / 12.0);            // midi_note_hz :284-287
         }
         DevMem d_sig;
@@ -174,10 +174,8 @@ int ow_alias_audit_run(const uint8_t* notes, const uint8_t* velocities, size_t n
             HIP_OK(hipMemcpy2DAsync(signals_out, signals_stride * sizeof(double), d_sig.p, total * sizeof(double), total * sizeof(double), n,
                                     hipMemcpyDeviceToHost, pool->stream));
         alias_audit_analyze_device(d_sig.as<double>(), n, total, total, AUDIT_SR, nominal.data(), pool->stream, out);
-        pool_destroy(pool);
         return 0;
     } catch (const std::exception& ex) {
-        if (pool) pool_destroy(pool);
         set_err(std::string("ow_alias_audit_run: ") + ex.what());
         return -1;
     }

@@ -112,7 +112,7 @@ long long ow_centroid_analyze(const double* signals, size_t n_rows, size_t strid
         if (frames_stride < g.frames) throw std::runtime_error("frames_stride smaller than the " + std::to_string(g.frames) + " frames of a row");
         require_device(device);
         StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
+        so.create();
         DevMem d_sig, d_hann, d_frames;
         const double* src = signals;
         if (!signals_is_device) {

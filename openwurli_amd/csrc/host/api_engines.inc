@@ -5,21 +5,21 @@ ow_engine* ow_engine_new(double sample_rate, int device, int preamp_kind) {
     ow_pool* p = ow_pool_new(sample_rate, 1, device, preamp_kind);
     if (!p) return nullptr;
     p->engines[0]->owns_pool = true;
-    return p->engines[0];
+    return p->engines[0].get();
 }
 ow_engine* ow_engine_new_kinds(double sample_rate, int device, int preamp_kind, int power_amp_kind, int tremolo_kind) {
     ow_pool* p = ow_pool_new_kinds(sample_rate, 1, device, preamp_kind, power_amp_kind, tremolo_kind);
     if (!p) return nullptr;
     p->engines[0]->owns_pool = true;
-    return p->engines[0];
+    return p->engines[0].get();
 }
 ow_engine* ow_engine_new_with(double sample_rate, int device, int preamp_kind, int power_amp_kind) {
     ow_pool* p = ow_pool_new_with(sample_rate, 1, device, preamp_kind, power_amp_kind);
     if (!p) return nullptr;
     p->engines[0]->owns_pool = true;
-    return p->engines[0];
+    return p->engines[0].get();
 }
-void ow_engine_free(ow_engine* e) { if (e && e->owns_pool) pool_destroy(e->pool); }
+void ow_engine_free(ow_engine* e) { if (e && e->owns_pool) delete e->pool; }
 // engine.rs:406-420.  No-ops / zeros on the behavioural amp, which has no separable rails (power_amp.rs:262-272).
 void ow_engine_set_rail_sag(ow_engine* e, int on) {
     if (!e || !e->pool || e->pool->power_amp_kind != OW_POWER_AMP_MELANGE) return;
@@ -154,7 +154,7 @@ int ow_engine_has_steal_voice_for(const ow_engine* e, uint8_t note) {
 }
 
 static void midi_apply_one(ow_pool* p, const ow_midi_event& ev) {
-    ow_engine* e = p->engines[ev.engine];
+    ow_engine* e = p->engines[ev.engine].get();
     switch (ev.type) {
         case 0: ow_engine_note_on(e, ev.note, ev.value); break;
         case 1: ow_engine_note_off(e, ev.note); break;
@@ -170,23 +170,19 @@ static bool midi_burst_on_device(ow_pool* p, const ow_midi_event* ev, size_t n) 
     HIP_OK(hipSetDevice(p->device));
     hipStream_t st = p->stream;
     if (!p->d_vm) {                                                // first burst: the device side of the state machine (instantiation-class work)
-        HIP_OK(hipMalloc(&p->d_vm, sizeof(OwVm) * I));
-        HIP_OK(hipMalloc(&p->d_ops_fix, sizeof(OwOp) * OW_VM_OPS_MAX * I));
-        HIP_OK(hipMalloc(&p->d_ev_begin, sizeof(uint32_t) * 2 * I));
-        HIP_OK(hipMalloc(&p->d_vm_ovf, sizeof(uint32_t)));
-        HIP_OK(hipHostMalloc(&p->h_vm_ovf, sizeof(uint32_t)));
+        DevBuf<OwVm> vm; DevBuf<OwOp> ops_fix; DevBuf<uint32_t> ev_begin, vm_ovf; PinBuf<uint32_t> h_vm_ovf;
+        vm.alloc(I); ops_fix.alloc(OW_VM_OPS_MAX * I); ev_begin.alloc(2 * I); vm_ovf.alloc(1); h_vm_ovf.alloc(1);
+        // all five or none: a burst that fails here leaves d_vm unset, and the next one sets up again
+        p->d_vm = std::move(vm); p->d_ops_fix = std::move(ops_fix); p->d_ev_begin = std::move(ev_begin); p->d_vm_ovf = std::move(vm_ovf); p->h_vm_ovf = std::move(h_vm_ovf);
         p->vm_host_dirty = 1;
     }
     if (__atomic_load_n(&p->host_ops_any, __ATOMIC_RELAXED)) return false;   // ops queued on the host come first in their engines' queues: host path
     // the events: straight from the caller's block when it is pinned (ow_host_alloc), else through a pinned staging copy made by the workers
     const ow_midi_event* src = (const ow_midi_event*)host_block_device_ptr(ev, sizeof(ow_midi_event) * n) ? ev : nullptr;
     if (n > p->ev_cap) {
-        if (p->d_ev) hipFree(p->d_ev);
-        if (p->h_ev) hipHostFree(p->h_ev);
-        p->d_ev = nullptr; p->h_ev = nullptr; p->ev_cap = 0;
+        p->ev_cap = 0;                                                              // until both exist
         const size_t cap = std::max<size_t>(n, (size_t)2 * OW_MAX_VOICES * I);      // a whole-keyboard re-strike of every engine
-        HIP_OK(hipMalloc(&p->d_ev, sizeof(ow_midi_event) * cap));
-        HIP_OK(hipHostMalloc(&p->h_ev, sizeof(ow_midi_event) * cap));
+        p->d_ev.alloc(cap); p->h_ev.alloc(cap);
         p->ev_cap = cap;
     }
     if (!src) {

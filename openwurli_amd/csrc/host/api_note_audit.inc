@@ -267,7 +267,7 @@ int ow_dft_magnitudes(const double* signals, size_t n_rows, size_t stride, size_
             throw std::runtime_error("rows or probe tables above the device-memory budget of " + std::to_string(note_audit::BUDGET_BYTES >> 30) + " GiB: call in parts");
         require_device(device);
         StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
+        so.create();
         DevMem d_sig, d_freqs, d_sums;
         const double* src = signals;
         if (!signals_is_device) {
@@ -375,7 +375,7 @@ int ow_debug_window_stats(const double* signals, size_t n_rows, size_t stride, c
         }
         require_device(device);
         StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
+        so.create();
         DevMem d_sig, d_out;
         d_sig.alloc(sizeof(double) * n_rows * stride);
         d_out.alloc(sizeof(double) * n_rows * n_windows);

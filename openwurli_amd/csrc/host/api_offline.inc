@@ -17,10 +17,9 @@ double ow_normalize_scale(const double* samples, size_t n) {     // main.rs:505-
 static long long render_note_impl(uint8_t midi, double velocity, double dur_s, double sample_rate, int device, double* out, size_t cap, const double* ds) {
     try {
         // a voices-only pool: no chain state, no Twin-T settle, and render_range launches the voice kernels alone
-        struct PoolGuard { ow_pool* p; ~PoolGuard() { pool_destroy(p); } } guard{pool_create(sample_rate, 1, device, OW_PREAMP_LEGACY8, OW_POWER_AMP_BEHAVIORAL,
-                                                                                               OW_TREMOLO_TWIN_T, true)};
-        ow_pool* p = guard.p;
-        ow_engine* e = p->engines[0];
+        std::unique_ptr<ow_pool> guard(pool_create(sample_rate, 1, device, OW_PREAMP_LEGACY8, OW_POWER_AMP_BEHAVIORAL, OW_TREMOLO_TWIN_T, true));
+        ow_pool* p = guard.get();
+        ow_engine* e = p->engines[0].get();
         // Voice::render_note: seed = midi * 2654435761, MLP off, no note clamping beyond the table range (voice.rs:206-207)
         const uint8_t note = std::min<uint8_t>(std::max<uint8_t>(midi, OW_MIDI_LO), OW_MIDI_HI);
         e->vm->has_voice |= 1ull; e->set_state(0, OW_VOICE_HELD); e->vm->midi_of[0] = note;
@@ -84,16 +83,13 @@ long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg*
         const bool overlap = job_chain_is_plain_legacy(cc, hj) && job_voice_overlap(n_jobs);
         DevMem m_prog;
         StreamOwner so2;
-        hipEvent_t ev_ready = nullptr, ev_voice = nullptr;
-        struct EvGuard { hipEvent_t* a; hipEvent_t* b; ~EvGuard() { if (*a) hipEventDestroy(*a); if (*b) hipEventDestroy(*b); } } evg{&ev_ready, &ev_voice};
+        Event ev_ready, ev_voice;
         int* d_prog = nullptr;
         if (overlap) {
             m_prog.alloc(sizeof(int) * (vblocks + 1));                 // progress of every voice block + the chain's "gave up waiting" flag
             d_prog = m_prog.as<int>();
             HIP_OK(hipMemsetAsync(d_prog, 0, sizeof(int) * (vblocks + 1), st));
-            HIP_OK(hipStreamCreateWithFlags(&so2.s, hipStreamNonBlocking));
-            HIP_OK(hipEventCreateWithFlags(&ev_ready, hipEventDisableTiming));
-            HIP_OK(hipEventCreateWithFlags(&ev_voice, hipEventDisableTiming));
+            so2.create(); ev_ready.create(); ev_voice.create();
             HIP_OK(hipEventRecord(ev_ready, st));
             HIP_OK(hipStreamWaitEvent(so2.s, ev_ready, 0));
             owdev::k_job_voice<<<dim3((unsigned)vblocks), dim3(64), 0, so2.s>>>(dK, d_nt, d_vrec, d_jobs, d_reed, (int)n_jobs, (long long)n, (long long)stride, d_prog);
@@ -237,7 +233,7 @@ int ow_extract_harmonics(const double* audio, size_t n_rows, size_t stride, doub
         }
         HIP_OK(hipSetDevice(device));
         StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
+        so.create();
         hipStream_t st = so.s;
         DevMem own_audio, m_xw, m_ss, m_segs, m_bins, m_peaks;   // released on every exit path
         const double* d_audio = audio;

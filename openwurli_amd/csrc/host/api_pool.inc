@@ -18,9 +18,9 @@ ow_pool* ow_pool_new_with(double sample_rate, size_t n_engines, int device, int 
     try { return pool_create(sample_rate, n_engines, device, preamp_kind, power_amp_kind); }
     catch (const std::exception& ex) { set_err(std::string("ow_pool_new_with: ") + ex.what()); return nullptr; }
 }
-void ow_pool_free(ow_pool* p) { pool_destroy(p); }
+void ow_pool_free(ow_pool* p) { delete p; }
 size_t ow_pool_size(const ow_pool* p) { return p ? p->I : 0; }
-ow_engine* ow_pool_engine(ow_pool* p, size_t i) { return (p && i < p->I) ? p->engines[i] : nullptr; }
+ow_engine* ow_pool_engine(ow_pool* p, size_t i) { return (p && i < p->I) ? p->engines[i].get() : nullptr; }
 ow_pool* ow_engine_pool(ow_engine* e) { return e ? e->pool : nullptr; }
 void* ow_pool_stream(ow_pool* p) { return p ? (void*)p->stream : nullptr; }
 void ow_pool_set_profiling(ow_pool* p, int on) { if (p) p->profiling = on != 0; }
@@ -31,7 +31,7 @@ int ow_pool_set_sample_rate(ow_pool* p, double sr) {
     try {
         HIP_OK(hipSetDevice(p->device));
         upload_consts(p, sr, p->hc.preamp_kind);
-        for (ow_engine* en : p->engines) {
+        for (auto& en : p->engines) {
             en->sr = sr;
             en->noise_on = false; en->thermal_gain = 1.0;   // set_sample_rate builds a new DkPreamp (engine.rs:276): noise off, gain 1.0
             en->rail_sag = true;                            // ... and a new PowerAmp (engine.rs:279): rail sag back on
@@ -50,7 +50,7 @@ void ow_pool_reset(ow_pool* p) {
     if (!p) return;
     guarded("ow_pool_reset", [&] {
         HIP_OK(hipSetDevice(p->device));
-        for (ow_engine* en : p->engines) engine_host_reset(en);
+        for (auto& en : p->engines) engine_host_reset(en.get());
         chain_init_range(p, 0, (int)p->I, INIT_RESET, std::vector<double>(p->I, 0.0));
         warm_up_range(p, 0, (int)p->I);
     });
@@ -70,7 +70,6 @@ void ow_pool_render(ow_pool* p, float* out_host, size_t out_stride, size_t len) 
     const bool ok = guarded("ow_pool_render", [&] {
         HIP_OK(hipSetDevice(p->device));
         if (p->inject_faults > 0) { --p->inject_faults; throw std::runtime_error("injected fault (ow_test_inject_render_faults)"); }
-        if (len > p->Lcap) { HIP_OK(hipStreamSynchronize(p->stream)); alloc_stream_buffers(p, len); }  // auto-grow, engine.rs:430
         const bool hostprof = p->sw.host_profile;
         auto t0 = std::chrono::steady_clock::now();
         render_range(p, 0, (int)p->I, len, true, out_host, out_stride);

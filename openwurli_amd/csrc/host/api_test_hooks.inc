@@ -84,7 +84,7 @@ int ow_debug_power_amp(double sample_rate, const double* in, size_t n_rows, size
         if (!in || !out || n_rows == 0 || n == 0 || !(sample_rate > 0.0)) throw std::runtime_error("bad argument");
         HIP_OK(hipSetDevice(device));
         StreamOwner so;
-        HIP_OK(hipStreamCreateWithFlags(&so.s, hipStreamNonBlocking));
+        so.create();
         std::unique_ptr<OwPaConsts> hc(new OwPaConsts());
         owhip::build_pa_consts(*hc, sample_rate);
         DevMem dC, dS, dIn, dOut, dT, dPa, dPn, dPv;
@@ -120,7 +120,7 @@ int ow_test_pool_enable_power_amp_tap(ow_pool* p) {
     if (!p || p->power_amp_kind != OW_POWER_AMP_MELANGE) return -1;
     if (p->d_pa_tap) return 0;
     if (hipSetDevice(p->device) != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess) return -1;
-    return hipMalloc(&p->d_pa_tap, sizeof(double) * 2 * p->Lcap * p->I) == hipSuccess ? 0 : -1;
+    try { p->d_pa_tap.alloc(2 * p->Lcap * p->I); return 0; } catch (const std::exception&) { return -1; }
 }
 int ow_test_pool_read_power_amp_out(ow_pool* p, double* out_host, size_t out_stride, size_t n_os) {
     if (!p || !out_host || !p->d_pa_tap || n_os > 2 * p->Lcap) return -1;
@@ -248,7 +248,7 @@ int ow_debug_trem_trajectory(double sample_rate, long long n_settle, long long n
         const size_t nck = TremTraj::ckpt_doubles((size_t)n);
         dck.alloc(sizeof(double) * nck); dbe.alloc(sizeof(unsigned long long) * (1 + OW_TRAJ_BE_CAP)); dzero.alloc(sizeof(uint32_t));
         StreamOwner so;
-        HIP_OK(hipStreamCreate(&so.s));
+        so.create(hipStreamDefault);
         HIP_OK(hipMemcpyAsync(dk.p, hc.get(), sizeof(OwConsts), hipMemcpyHostToDevice, so.s));
         HIP_OK(hipMemsetAsync(dck.p, 0, sizeof(double) * nck, so.s));
         HIP_OK(hipMemsetAsync(dbe.p, 0xFF, sizeof(unsigned long long) * (1 + OW_TRAJ_BE_CAP), so.s));
@@ -270,8 +270,8 @@ int ow_debug_trem_trajectory(double sample_rate, long long n_settle, long long n
         unsigned long long cold0[2] = {0, 0}, cold1[2] = {0, 0};
         HIP_OK(hipStreamSynchronize(so.s));
         HIP_OK(hipMemcpyFromSymbol(cold0, HIP_SYMBOL(owdev::g_trem_row_cold), sizeof cold0));
-        hipEvent_t e0, e1;
-        HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1));
+        Event e0, e1;
+        e0.create(hipEventDefault); e1.create(hipEventDefault);
         HIP_OK(hipEventRecord(e0, so.s));
         for (long long t = 0; t < n; t += chunk) {
             const long long m = std::min(chunk, n - t);
@@ -283,7 +283,6 @@ int ow_debug_trem_trajectory(double sample_rate, long long n_settle, long long n
         HIP_OK(hipStreamSynchronize(so.s));
         float ms = 0.0f;
         HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-        hipEventDestroy(e0); hipEventDestroy(e1);
         if (ms_out) *ms_out = ms;
         HIP_OK(hipMemcpyFromSymbol(cold1, HIP_SYMBOL(owdev::g_trem_row_cold), sizeof cold1));
         if (cold_out) { cold_out[0] = cold1[0] - cold0[0]; cold_out[1] = cold1[1] - cold0[1]; }     // (of the trajectory launches; another store extending meanwhile would add its own)
@@ -304,6 +303,10 @@ int ow_test_host_melange_paths(double rate) {
         return (c->ml_ok ? 1 : 0) | (c->ml_sparse_ok ? 2 : 0);
     } catch (const std::exception& ex) { set_err(std::string("ow_test_host_melange_paths: ") + ex.what()); return -1; }
 }
+// The k-th acquisition (0-based) this thread makes from now on through the owning types of host_base.inc throws instead of calling HIP,
+// then the hook disarms itself; k < 0 disarms it.  ow_test_live_resources: what is owned through those types right now, process-wide.
+void ow_test_fail_acquire_after(int k) { g_fail_acquire_after = k < 0 ? -1 : k; }
+uint64_t ow_test_live_resources(void) { return g_live_resources.load(std::memory_order_relaxed); }
 void ow_test_inject_render_faults(ow_pool* p, int n_renders) { if (p) p->inject_faults = n_renders > 0 ? n_renders : 0; }
 // One latched switch of a live pool (struct Switches; the OW_* environment variables are only read when a pool is created).
 int ow_test_pool_set_switch(ow_pool* p, const char* name, int value) {

@@ -40,18 +40,54 @@ void* host_block_device_ptr(const void* ptr, size_t bytes) {
     return (char*)it->second.dptr + off;
 }
 
-struct DevMem {   // device buffer released on every exit path
+// Owning handles: device buffer, pinned host buffer, event, stream.  Each is move-only, releases on every exit path, and is the ONE place
+// that acquires and releases its kind of resource.  Every acquisition passes acquiring() first and counts itself afterwards -- the two
+// test hooks ow_test_fail_acquire_after / ow_test_live_resources (openwurli_hip_test.h); neither happens during a steady render.
+std::atomic<uint64_t> g_live_resources{0};
+thread_local int g_fail_acquire_after = -1;
+void acquiring() {
+    if (g_fail_acquire_after >= 0 && g_fail_acquire_after-- == 0) throw std::runtime_error("ow_test_fail_acquire_after: injected acquisition failure");
+}
+void live(int d) { g_live_resources.fetch_add((uint64_t)(int64_t)d, std::memory_order_relaxed); }
+#define OW_OWNER(T, h)                                                                 \
+    T() = default;                                                                     \
+    T(T&& o) noexcept : h(o.h) { o.h = nullptr; }                                      \
+    T& operator=(T&& o) noexcept { std::swap(h, o.h); return *this; } /* o releases what this held */ \
+    ~T() { reset(); }
+struct DevMem {
     void* p = nullptr;
-    DevMem() = default;
-    DevMem(const DevMem&) = delete;
-    DevMem& operator=(const DevMem&) = delete;
-    ~DevMem() { if (p) hipFree(p); }
+    OW_OWNER(DevMem, p)
+    void reset() { if (p) { hipFree(p); p = nullptr; live(-1); } }
+    void alloc(size_t bytes) { reset(); acquiring(); HIP_OK(hipMalloc(&p, std::max<size_t>(bytes, 8))); live(1); }
+    void* release() { void* q = p; if (q) live(-1); p = nullptr; return q; }     // hands the buffer to an owner outside these types (TremTraj)
     template <class T> T* as() const { return static_cast<T*>(p); }
-    void alloc(size_t bytes) { HIP_OK(hipMalloc(&p, std::max<size_t>(bytes, 8))); }
+};
+struct PinMem {
+    void* p = nullptr;
+    OW_OWNER(PinMem, p)
+    void reset() { if (p) { hipHostFree(p); p = nullptr; live(-1); } }
+    void alloc(size_t bytes) { reset(); acquiring(); HIP_OK(hipHostMalloc(&p, bytes)); live(1); }
+};
+// n elements of T in device (DevBuf) / pinned host (PinBuf) memory; reads as the raw T* wherever one is expected
+template <class T, class Mem> struct Typed : Mem {
+    void alloc(size_t n) { Mem::alloc(sizeof(T) * n); }
+    operator T*() const { return static_cast<T*>(this->p); }
+};
+template <class T> using DevBuf = Typed<T, DevMem>;
+template <class T> using PinBuf = Typed<T, PinMem>;
+struct Event {
+    hipEvent_t e = nullptr;
+    OW_OWNER(Event, e)
+    void reset() { if (e) { hipEventDestroy(e); e = nullptr; live(-1); } }
+    void create(unsigned flags = hipEventDisableTiming) { reset(); acquiring(); HIP_OK(hipEventCreateWithFlags(&e, flags)); live(1); }
+    operator hipEvent_t() const { return e; }
 };
 struct StreamOwner {
     hipStream_t s = nullptr;
-    ~StreamOwner() { if (s) hipStreamDestroy(s); }
+    OW_OWNER(StreamOwner, s)
+    void reset() { if (s) { hipStreamDestroy(s); s = nullptr; live(-1); } }
+    void create(unsigned flags = hipStreamNonBlocking) { reset(); acquiring(); HIP_OK(hipStreamCreateWithFlags(&s, flags)); live(1); }
+    operator hipStream_t() const { return s; }
 };
 
 // Persistent host worker threads.  The realtime entry points (ow_pool_render, ow_pool_midi) must not allocate once capacity is

@@ -45,7 +45,6 @@ static void launch_job_chain_legacy(const OwConsts* dK, const owdev::OwJobDev* d
 }
 
 ow_pool* pool_create(double sample_rate, size_t n_engines, int device, int preamp_kind, int power_amp_kind, int tremolo_kind, bool voices_only, bool no_traj = false);
-void pool_destroy(ow_pool* p);
 
 // The chain of the job paths (`preamp-bench render` / `render-midi`, tools/preamp-bench/src/main.rs:413-497, 1880-1890) for n_jobs rows
 // of voice signal d_in -> d_out (both [n_jobs][stride]), with everything the commands' flags can ask for:
@@ -102,12 +101,11 @@ void run_job_chain(OfflineCall& call, const JobChainCfg& cfg, const std::vector<
         }
         if (!trem) {                                        // longer than the store: one oscillator for this call, from a pool of one
             d_r.alloc(sizeof(double) * (size_t)n_os);
-            struct PoolGuard { ow_pool* p; ~PoolGuard() { pool_destroy(p); } } g{pool_create(cfg.sample_rate, 1, cfg.device, OW_PREAMP_LEGACY8, OW_POWER_AMP_BEHAVIORAL,
-                                                                                                 OW_TREMOLO_TWIN_T, false, /*no_traj=*/true)};
+            std::unique_ptr<ow_pool> g(pool_create(cfg.sample_rate, 1, cfg.device, OW_PREAMP_LEGACY8, OW_POWER_AMP_BEHAVIORAL, OW_TREMOLO_TWIN_T, false, /*no_traj=*/true));
             // the fresh pool's oscillator rows are Tremolo::new's settled state; n_os steps of Tremolo::process, R written per step
-            owdev::k_tremolo_wide<false><<<dim3(1), dim3(64), 0, g.p->stream>>>(g.p->dK, g.p->d_cs, d_r.as<double>(), 1, n_os, g.p->d_leaders, 1);
+            owdev::k_tremolo_wide<false><<<dim3(1), dim3(64), 0, g->stream>>>(g->dK, g->d_cs, d_r.as<double>(), 1, n_os, g->d_leaders, 1);
             HIP_OK(hipGetLastError());
-            HIP_OK(hipStreamSynchronize(g.p->stream));
+            HIP_OK(hipStreamSynchronize(g->stream));
             trem = d_r.as<double>();
         }
     }

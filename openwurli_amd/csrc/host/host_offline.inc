@@ -75,7 +75,7 @@ struct OfflineCall {
     OfflineCall(int device, double sr, int preamp_kind, bool note_table) : device_(device), hc_(new OwConsts()) {
         require_device(device);
         owhip::build_consts(*hc_, sr, preamp_kind);
-        HIP_OK(hipStreamCreateWithFlags(&so_.s, hipStreamNonBlocking));
+        so_.create();
         m_K_.alloc(sizeof(OwConsts));
         HIP_OK(hipMemcpyAsync(m_K_.p, hc_.get(), sizeof(OwConsts), hipMemcpyHostToDevice, so_.s));
         if (note_table) {

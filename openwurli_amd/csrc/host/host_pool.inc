@@ -94,7 +94,7 @@ void trem_evict(ow_pool* p, int e0, int ne, int n_os) {
         for (size_t i = 0; i < eng.size(); ++i) be[i] = T->be_count_at(tp[i], events);
     }
     // scratch reserved at pool creation (d_evict: [I] engines as u64 | [I] t | [I] fallback counts): no allocation on this path
-    uint32_t* de = (uint32_t*)p->d_evict; long long* dt = (long long*)(p->d_evict + p->I); unsigned long long* db = p->d_evict + 2 * p->I;
+    uint32_t* de = (uint32_t*)p->d_evict.p; long long* dt = (long long*)(p->d_evict + p->I); unsigned long long* db = p->d_evict + 2 * p->I;
     HIP_OK(hipMemcpy(de, eng.data(), sizeof(uint32_t) * eng.size(), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(dt, tp.data(), sizeof(long long) * eng.size(), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(db, be.data(), sizeof(unsigned long long) * eng.size(), hipMemcpyHostToDevice));
@@ -139,7 +139,7 @@ void chain_init_range(ow_pool* p, int e0, int ne, int mode, const std::vector<do
         // (engine.rs:86-99) -- also for a setter call the device has not seen yet because no block was rendered since.  Hand the
         // host targets to the kernel; the retarget requests themselves are dropped by engine_host_reset.
         for (int k = 0; k < ne; ++k) {
-            const ow_engine* en = p->engines[e0 + k];
+            const ow_engine* en = p->engines[e0 + k].get();
             p->h_snap[0 * p->I + e0 + k] = en->depth.target; p->h_snap[1 * p->I + e0 + k] = en->spk.target; p->h_snap[2 * p->I + e0 + k] = en->volume.target;
         }
         for (int r = 0; r < 3; ++r)
@@ -366,6 +366,7 @@ static void launch_tremolo(ow_pool* p, hipStream_t tt, double* rbuf, int n_os) {
 // (warm-up of engines whose voices were just freed).
 // out_host != nullptr: rows [e0, e0+ne) of the block are copied to out_host[(e - e0) * out_stride] as their stages finish.
 void render_range(ow_pool* p, int e0, int ne, size_t len, bool with_voices, float* out_host = nullptr, size_t out_stride = 0) {
+    if (len > p->Lcap) { HIP_OK(hipStreamSynchronize(p->stream)); alloc_stream_buffers(p, len); }  // auto-grow, engine.rs:430 (also after a grow that failed: Lcap 0)
     const int I = (int)p->I;
     const int L = (int)len, Lcap = (int)p->Lcap;
     p->out_ld = len;
@@ -490,7 +491,7 @@ void render_range(ow_pool* p, int e0, int ne, size_t len, bool with_voices, floa
                     if (a.op_count || a.set_flags) { a.op_count = 0; a.set_flags = 0; }
                     continue;
                 }
-                ow_engine* en = p->engines[e0 + k];
+                ow_engine* en = p->engines[e0 + k].get();
                 // engine.rs:471-473: a Free slot renders nothing unless it still carries a steal voice
                 a.main_mask = en->vm->main_mask; a.steal_mask = en->vm->steal_mask;
                 a.noise_on = en->noise_on ? 1u : 0u; a.thermal_gain = en->thermal_gain;
@@ -812,7 +813,7 @@ void guard_second_pass(ow_pool* p, const uint32_t* engs, size_t n_eng, size_t le
     hipStream_t st = p->stream;
     uint32_t nm = 0, ns = 0;          // entries; one block per engine and list
     for (size_t i = 0; i < n_eng; ++i) {
-        const ow_engine* en = p->engines[engs[i]];
+        const ow_engine* en = p->engines[engs[i]].get();
         auto put = [&](uint32_t* a, uint32_t& n, uint64_t mask) {
             if (!mask) return;
             for (uint64_t m = mask; m; m &= m - 1) a[n++] = (engs[i] << 6) | (uint32_t)__builtin_ctzll(m);
@@ -845,7 +846,7 @@ void guard_second_pass(ow_pool* p, const uint32_t* engs, size_t n_eng, size_t le
     for (size_t i = 0; i < n_eng; ++i) {
         OwEngineOut& o = p->h_eout[engs[i]];
         o = p->h_eout_packed[i];
-        engine_guard_second_pass_result(p->engines[engs[i]], o);
+        engine_guard_second_pass_result(p->engines[engs[i]].get(), o);
         p->transient[engs[i]] = o.transient != 0u;
         o.sum_nonfinite = 1u;         // the block's voice sum stays "zeroed by the guard" for ow_pool_read_voice_sum
     }
@@ -865,7 +866,7 @@ void steal_countdown_early(ow_pool* p, size_t len) {
     auto slice = [&](size_t t) {
         const int k1 = std::min(ne, (int)(t + 1) * per);
         for (int k = (int)t * per; k < k1; ++k)
-            if (p->h_args[k].steal_mask) engine_steal_countdown(p->engines[k], l32);
+            if (p->h_args[k].steal_mask) engine_steal_countdown(p->engines[k].get(), l32);
     };
     Workers::get().each(T, slice);
     p->steal_counted = true;
@@ -887,7 +888,7 @@ void post_render_host(ow_pool* p, int e0, int ne, size_t len) {
         // fast path on the contiguous status/args arrays: nothing to book-keep for this engine
         if ((steal_counted || !a.steal_mask) && !(o.silent_mask & a.main_mask) && !o.sum_nonfinite && !o.out_nonfinite) return r;
         if (o.sum_nonfinite) r |= 4;
-        engine_post_render(p->engines[e], l32, o, steal_counted);
+        engine_post_render(p->engines[e].get(), l32, o, steal_counted);
         return r;
     };
     auto second_pass = [&] {   // voice-sum NaN guard fired somewhere: the reference's second render pass for those engines
@@ -1004,108 +1005,99 @@ ow_pool* pool_create(double sample_rate, size_t n_engines, int device, int pream
     if (tremolo_kind != OW_TREMOLO_TWIN_T && tremolo_kind != OW_TREMOLO_LEGACY_LFO) throw std::runtime_error("unknown tremolo_kind");
     require_known_kinds(preamp_kind, power_amp_kind);
     require_device(device);
-    ow_pool* p = new ow_pool();
+    std::unique_ptr<ow_pool> owner(new ow_pool());     // a throw below releases everything acquired so far
+    ow_pool* p = owner.get();
     p->device = device;
     p->I = n_engines;
     p->power_amp_kind = power_amp_kind;
     p->tremolo_kind = tremolo_kind;
     p->voices_only = voices_only;
-    HIP_OK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    HIP_OK(hipStreamCreateWithFlags(&p->stream_trem, hipStreamNonBlocking));
-    for (auto& e : p->ev) HIP_OK(hipEventCreate(&e));
-    p->pipe_stream[0] = p->stream;
-    for (int k = 1; k < OW_MAX_STAGES; ++k) HIP_OK(hipStreamCreateWithFlags(&p->pipe_stream[k], hipStreamNonBlocking));
-    HIP_OK(hipEventCreateWithFlags(&p->ev_ready, hipEventDisableTiming));
+    p->pipe_stream[0].create();
+    p->stream = p->pipe_stream[0];
+    p->stream_trem.create();
+    for (auto& e : p->ev) e.create(hipEventDefault);
+    for (int k = 1; k < OW_MAX_STAGES; ++k) p->pipe_stream[k].create();
+    p->ev_ready.create();
     for (int k = 0; k < OW_MAX_STAGES; ++k) {
-        HIP_OK(hipEventCreateWithFlags(&p->ev_voice_done[k], hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&p->ev_stage_done[k], hipEventDisableTiming));
-        for (auto& e : p->ev_stage[k]) HIP_OK(hipEventCreate(&e));
+        p->ev_voice_done[k].create();
+        p->ev_stage_done[k].create();
+        for (auto& e : p->ev_stage[k]) e.create(hipEventDefault);
     }
-    for (auto& e : p->ev_trem) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_OK(hipMalloc(&p->d_trem_backup, sizeof(double) * 18 * n_engines));
-    HIP_OK(hipMalloc(&p->d_trem_settled, sizeof(double) * 18));
-    HIP_OK(hipMalloc(&p->d_zero, sizeof(uint32_t)));
+    for (auto& e : p->ev_trem) e.create();
+    p->d_trem_backup.alloc(18 * n_engines);
+    p->d_trem_settled.alloc(18);
+    p->d_zero.alloc(1);
     HIP_OK(hipMemsetAsync(p->d_zero, 0, sizeof(uint32_t), p->stream));
-    HIP_OK(hipMalloc(&p->d_birth, sizeof(long long) * n_engines));
-    HIP_OK(hipMalloc(&p->d_evict, sizeof(unsigned long long) * 3 * n_engines));
+    p->d_birth.alloc(n_engines);
+    p->d_evict.alloc(3 * n_engines);
     p->h_birth.assign(n_engines, OW_OFF_TRAJ);
     p->sw = Switches::from_env();
     if (no_traj) p->sw.trem_traj = false;
-    HIP_OK(hipMalloc(&p->dK, sizeof(OwConsts)));
-    HIP_OK(hipMalloc(&p->dK48, sizeof(OwConsts)));
-    HIP_OK(hipMalloc(&p->d_nt, sizeof(double) * NT_COUNT * 64));
-    HIP_OK(hipMalloc(&p->d_vrec, sizeof(double) * n_engines * 2 * OW_VREC_DOUBLES));
-    HIP_OK(hipMalloc(&p->d_cs, sizeof(double) * CS_COUNT * n_engines));
-    HIP_OK(hipMalloc(&p->d_args, sizeof(OwEngineArgs) * n_engines));
-    HIP_OK(hipMalloc(&p->d_eout, sizeof(OwEngineOut) * n_engines));
-    HIP_OK(hipHostMalloc(&p->h_args, sizeof(OwEngineArgs) * n_engines));
-    HIP_OK(hipHostMalloc(&p->h_vm, sizeof(OwVm) * n_engines));
-    HIP_OK(hipEventCreateWithFlags(&p->ev_vm, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&p->ev_vm_events, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&p->ev_vm_up, hipEventDisableTiming));
-    HIP_OK(hipHostMalloc(&p->h_eout, sizeof(OwEngineOut) * n_engines));
-    HIP_OK(hipMalloc(&p->d_eout_packed, sizeof(OwEngineOut) * n_engines));
-    HIP_OK(hipHostMalloc(&p->h_eout_packed, sizeof(OwEngineOut) * n_engines));
-    HIP_OK(hipMalloc(&p->d_skew_seen, sizeof(uint32_t)));
+    p->dK.alloc(1);
+    p->dK48.alloc(1);
+    p->d_nt.alloc(NT_COUNT * 64);
+    p->d_vrec.alloc(n_engines * 2 * OW_VREC_DOUBLES);
+    p->d_cs.alloc(CS_COUNT * n_engines);
+    p->d_args.alloc(n_engines);
+    p->d_eout.alloc(n_engines);
+    p->h_args.alloc(n_engines);
+    p->h_vm.alloc(n_engines);
+    p->ev_vm.create(); p->ev_vm_events.create(); p->ev_vm_up.create();
+    p->h_eout.alloc(n_engines);
+    p->d_eout_packed.alloc(n_engines); p->h_eout_packed.alloc(n_engines);
+    p->d_skew_seen.alloc(1);
     HIP_OK(hipMemset(p->d_skew_seen, 0, sizeof(uint32_t)));
-    HIP_OK(hipHostMalloc(&p->h_skew_seen, sizeof(uint32_t)));
+    p->h_skew_seen.alloc(1);
     *p->h_skew_seen = 0u;
     if (n_engines >= 64) {      // status summary of big ranges (k_eout_attention)
-        HIP_OK(hipMalloc(&p->d_attn, sizeof(uint64_t) * ((n_engines + 63) / 64)));
-        HIP_OK(hipHostMalloc(&p->h_attn, sizeof(uint64_t) * ((n_engines + 63) / 64)));
-        HIP_OK(hipMalloc(&p->d_prev_tr, n_engines));
+        p->d_attn.alloc((n_engines + 63) / 64); p->h_attn.alloc((n_engines + 63) / 64);
+        p->d_prev_tr.alloc(n_engines);
         HIP_OK(hipMemset(p->d_prev_tr, 0, n_engines));
-        HIP_OK(hipHostMalloc(&p->h_prev_tr, n_engines));
+        p->h_prev_tr.alloc(n_engines);
         p->eout_live.reserve(n_engines / 8 + 64);       // the summary path lists at most ne / 8 engines: nothing grows on the render path
     }
     for (ow_pool::VoiceList* vl : {&p->vl_steady, &p->vl_general, &p->vl_steal, &p->vl_attack}) {   // worst case: one block per engine
-        HIP_OK(hipMalloc(&vl->d, sizeof(uint32_t) * 64 * n_engines));
-        HIP_OK(hipHostMalloc(&vl->h, sizeof(uint32_t) * 64 * n_engines));
+        vl->d.alloc(64 * n_engines); vl->h.alloc(64 * n_engines);
     }
     p->transient.assign(n_engines, 0);
-    HIP_OK(hipMalloc(&p->d_lead, sizeof(uint32_t) * n_engines));
-    HIP_OK(hipHostMalloc(&p->h_lead, sizeof(uint32_t) * n_engines));
-    HIP_OK(hipMalloc(&p->d_leaders, sizeof(uint32_t) * n_engines));
-    HIP_OK(hipHostMalloc(&p->h_leaders, sizeof(uint32_t) * n_engines));
-    HIP_OK(hipMalloc(&p->d_copy, sizeof(uint32_t) * 2 * n_engines));
-    HIP_OK(hipHostMalloc(&p->h_copy, sizeof(uint32_t) * 2 * n_engines));
+    p->d_lead.alloc(n_engines); p->h_lead.alloc(n_engines);
+    p->d_leaders.alloc(n_engines); p->h_leaders.alloc(n_engines);
+    p->d_copy.alloc(2 * n_engines); p->h_copy.alloc(2 * n_engines);
     p->grp_in.assign(n_engines, 0); p->grp_out.assign(n_engines, 0);
     for (size_t i = 0; i < n_engines; ++i) p->h_lead[i] = (uint32_t)i;   // singletons until the chain state is replicated below
-    HIP_OK(hipMalloc(&p->d_snap, sizeof(double) * 3 * n_engines));
-    HIP_OK(hipHostMalloc(&p->h_snap, sizeof(double) * 3 * n_engines));
+    p->d_snap.alloc(3 * n_engines); p->h_snap.alloc(3 * n_engines);
     ensure_ops_capacity(p, (size_t)3 * OW_MAX_VOICES * n_engines);   // a whole-keyboard re-strike of every engine: no allocation in render
     Workers::get();                                                  // start the host worker threads now, not inside the first render
-    HIP_OK(hipMalloc(&p->d_op_engines, sizeof(uint32_t) * n_engines));
-    HIP_OK(hipHostMalloc(&p->h_op_engines, sizeof(uint32_t) * n_engines));
+    p->d_op_engines.alloc(n_engines); p->h_op_engines.alloc(n_engines);
     std::memset(p->h_args, 0, sizeof(OwEngineArgs) * n_engines);
     std::memset(p->h_eout, 0, sizeof(OwEngineOut) * n_engines);
     HIP_OK(hipMemsetAsync(p->d_vrec, 0, sizeof(double) * n_engines * 2 * OW_VREC_DOUBLES, p->stream));
     HIP_OK(hipMemsetAsync(p->d_cs, 0, sizeof(double) * CS_COUNT * n_engines, p->stream));
     alloc_stream_buffers(p, n_engines == 1 ? (size_t)OW_MAX_BLOCK : (size_t)1024);  // engine.rs:25 MAX_BLOCK_SIZE for a lone engine
     if (power_amp_kind == OW_POWER_AMP_MELANGE) {
-        HIP_OK(hipMalloc(&p->dPa, sizeof(OwPaConsts)));
-        HIP_OK(hipMalloc(&p->d_pa, sizeof(double) * owdev::PAS_COUNT * n_engines));
+        p->dPa.alloc(1);
+        p->d_pa.alloc(owdev::PAS_COUNT * n_engines);
         HIP_OK(hipMemsetAsync(p->d_pa, 0, sizeof(double) * owdev::PAS_COUNT * n_engines, p->stream));
-        HIP_OK(hipMalloc(&p->d_pa_settled, sizeof(double) * owdev::PAS_CIRCUIT_END));
+        p->d_pa_settled.alloc(owdev::PAS_CIRCUIT_END);
         pa_settled_to_device(device, p->d_pa_settled, p->stream);
-        HIP_OK(hipMalloc(&p->d_pa_demand, sizeof(uint32_t) * n_engines));
+        p->d_pa_demand.alloc(n_engines);
         HIP_OK(hipMemsetAsync(p->d_pa_demand, 0, sizeof(uint32_t) * n_engines, p->stream));
-        HIP_OK(hipMalloc(&p->d_pa_order, sizeof(uint32_t) * n_engines));
-        HIP_OK(hipMalloc(&p->d_pa_hist, sizeof(uint32_t) * PA_ORDER_CLASSES * OW_MAX_STAGES));
+        p->d_pa_order.alloc(n_engines);
+        p->d_pa_hist.alloc(PA_ORDER_CLASSES * OW_MAX_STAGES);
     }
     upload_consts(p, sample_rate, preamp_kind);
     owdev::k_note_table<<<dim3(1), dim3(64), 0, p->stream>>>(p->d_nt);
     if (preamp_kind == OW_PREAMP_MELANGE12) {
-        HIP_OK(hipMalloc(&p->d_mel_settled, sizeof(double) * 18));
+        p->d_mel_settled.alloc(18);
         // LU workspace of the generic rebuild (the fallback of both literal kernels): the column-streamed kernel wants one [144] column
         // per lane = (engine, state), lane-minor, + 32 spare engines for the masked lanes of a last partial wavefront; the LDS-matrix
         // kernel one [144][32] slab per workgroup
         p->mel_lu_ld = 2 * (n_engines + 32);
-        HIP_OK(hipMalloc(&p->d_mel_lu, sizeof(double) * 144 * std::max<size_t>(p->mel_lu_ld, 32 * ((size_t)(n_engines + 31) / 32 + OW_MAX_SLICES + 1))));
+        p->d_mel_lu.alloc(144 * std::max<size_t>(p->mel_lu_ld, 32 * ((size_t)(n_engines + 31) / 32 + OW_MAX_SLICES + 1)));
         mel_settled_to_device(device, p->d_mel_settled, p->stream);
         // Noise streams: the reference clones one process-wide state whose RNGs were seeded from the clock (master seed 0,
         // gen_preamp.rs:1512-1521 via melange_adapter.rs:12-29), so every engine of a process starts on the same streams.
-        HIP_OK(hipMalloc(&p->d_noise, sizeof(double) * NZ_COUNT * n_engines));
+        p->d_noise.alloc(NZ_COUNT * n_engines);
         HIP_OK(hipMemsetAsync(p->d_noise, 0, sizeof(double) * NZ_COUNT * n_engines, p->stream));
         std::vector<uint64_t> seeds(n_engines, process_noise_seed());
         HIP_OK(hipMemcpyAsync(p->d_noise + (size_t)NZ_SEED * n_engines, seeds.data(), sizeof(uint64_t) * n_engines, hipMemcpyHostToDevice, p->stream));
@@ -1114,7 +1106,7 @@ ow_pool* pool_create(double sample_rate, size_t n_engines, int device, int pream
     p->engines.resize(n_engines);
     p->dirty.assign(n_engines, 1);
     for (size_t i = 0; i < n_engines; ++i) {
-        ow_engine* en = new ow_engine();
+        ow_engine* en = (p->engines[i] = std::make_unique<ow_engine>()).get();
         en->pool = p;
         en->index = i;
         en->dirty = &p->dirty[i]; en->dirty_any = &p->dirty_any;
@@ -1126,12 +1118,11 @@ ow_pool* pool_create(double sample_rate, size_t n_engines, int device, int pream
         // from 64 to 192 entries inside the first re-strike cost 180 ms of reallocation and page faults on the MIDI threads
         // (later ones take 8 ms).  Same reason as ensure_buffer_capacity: no allocation where the events arrive.
         en->ops.reserve(3 * OW_MAX_VOICES);
-        p->engines[i] = en;
     }
     if (voices_only) {          // Voice::render_note has no chain (voice.rs:191-221): nothing to initialise, nothing to settle
         for (size_t i = 0; i < n_engines; ++i) p->h_lead[i] = 0u;
         HIP_OK(hipStreamSynchronize(p->stream));
-        return p;
+        return owner.release();
     }
     // WurliEngine::new for engine 0 on the device, then replicate (every engine of a fresh pool is identical)
     chain_init_range(p, 0, 1, INIT_NEW, std::vector<double>(1, 0.5));
@@ -1151,77 +1142,7 @@ ow_pool* pool_create(double sample_rate, size_t n_engines, int device, int pream
         owdev::k_mel_noise_seed<<<dim3((unsigned)((n_engines + 63) / 64)), dim3(64), 0, p->stream>>>(p->d_noise, (int)n_engines, 0, (int)n_engines);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(p->stream));
-    return p;
-}
-
-void pool_destroy(ow_pool* p) {
-    if (!p) return;
-    hipSetDevice(p->device);
-    if (p->stream) hipStreamSynchronize(p->stream);
-    free_stream_buffers(p);
-    hipFree(p->dK); hipFree(p->dK48); hipFree(p->d_nt); hipFree(p->d_vrec); hipFree(p->d_cs);
-    if (p->d_mel_settled) hipFree(p->d_mel_settled);
-    if (p->d_mel_lu) hipFree(p->d_mel_lu);
-    if (p->d_noise) hipFree(p->d_noise);
-    if (p->dPa) hipFree(p->dPa);
-    if (p->d_pa) hipFree(p->d_pa);
-    if (p->d_pa_settled) hipFree(p->d_pa_settled);
-    if (p->d_pa_tap) hipFree(p->d_pa_tap);
-    if (p->d_pa_demand) hipFree(p->d_pa_demand);
-    if (p->d_pa_order) hipFree(p->d_pa_order);
-    if (p->d_pa_hist) hipFree(p->d_pa_hist);
-    hipFree(p->d_args); hipFree(p->d_eout);
-    if (p->d_ops) hipFree(p->d_ops);
-    if (p->h_ops) hipHostFree(p->h_ops);
-    for (ow_pool::VoiceList* vl : {&p->vl_steady, &p->vl_general, &p->vl_steal, &p->vl_attack}) { if (vl->d) hipFree(vl->d); if (vl->h) hipHostFree(vl->h); }
-    if (p->d_op_engines) hipFree(p->d_op_engines);
-    if (p->h_op_engines) hipHostFree(p->h_op_engines);
-    if (p->d_lead) hipFree(p->d_lead);
-    if (p->h_lead) hipHostFree(p->h_lead);
-    if (p->d_leaders) hipFree(p->d_leaders);
-    if (p->h_leaders) hipHostFree(p->h_leaders);
-    if (p->d_copy) hipFree(p->d_copy);
-    if (p->h_copy) hipHostFree(p->h_copy);
-    if (p->d_snap) hipFree(p->d_snap);
-    if (p->h_snap) hipHostFree(p->h_snap);
-    hipHostFree(p->h_args); hipHostFree(p->h_eout);
-    if (p->h_vm) hipHostFree(p->h_vm);
-    if (p->d_vm) hipFree(p->d_vm);
-    if (p->d_ops_fix) hipFree(p->d_ops_fix);
-    if (p->h_ev) hipHostFree(p->h_ev);
-    if (p->d_ev) hipFree(p->d_ev);
-    if (p->d_ev_begin) hipFree(p->d_ev_begin);
-    if (p->d_vm_ovf) hipFree(p->d_vm_ovf);
-    if (p->h_vm_ovf) hipHostFree(p->h_vm_ovf);
-    if (p->ev_vm) hipEventDestroy(p->ev_vm);
-    if (p->ev_vm_events) hipEventDestroy(p->ev_vm_events);
-    if (p->ev_vm_up) hipEventDestroy(p->ev_vm_up);
-    if (p->d_eout_packed) hipFree(p->d_eout_packed);
-    if (p->h_eout_packed) hipHostFree(p->h_eout_packed);
-    if (p->d_skew_seen) hipFree(p->d_skew_seen);
-    if (p->h_skew_seen) hipHostFree(p->h_skew_seen);
-    if (p->d_attn) hipFree(p->d_attn);
-    if (p->h_attn) hipHostFree(p->h_attn);
-    if (p->d_prev_tr) hipFree(p->d_prev_tr);
-    if (p->h_prev_tr) hipHostFree(p->h_prev_tr);
-    for (auto& e : p->ev) if (e) hipEventDestroy(e);
-    for (int k = 1; k < OW_MAX_STAGES; ++k) if (p->pipe_stream[k]) { hipStreamSynchronize(p->pipe_stream[k]); hipStreamDestroy(p->pipe_stream[k]); }
-    if (p->ev_ready) hipEventDestroy(p->ev_ready);
-    for (int k = 0; k < OW_MAX_STAGES; ++k) {
-        if (p->ev_voice_done[k]) hipEventDestroy(p->ev_voice_done[k]);
-        if (p->ev_stage_done[k]) hipEventDestroy(p->ev_stage_done[k]);
-        for (auto& e : p->ev_stage[k]) if (e) hipEventDestroy(e);
-    }
-    for (auto& e : p->ev_trem) if (e) hipEventDestroy(e);
-    if (p->d_trem_backup) hipFree(p->d_trem_backup);
-    if (p->d_trem_settled) hipFree(p->d_trem_settled);
-    if (p->d_zero) hipFree(p->d_zero);
-    if (p->d_birth) hipFree(p->d_birth);
-    if (p->d_evict) hipFree(p->d_evict);
-    if (p->stream_trem) hipStreamDestroy(p->stream_trem);
-    if (p->stream) hipStreamDestroy(p->stream);
-    for (ow_engine* en : p->engines) delete en;
-    delete p;
+    return owner.release();
 }
 
 template <typename F>

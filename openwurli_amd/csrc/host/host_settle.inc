@@ -19,28 +19,19 @@ void invalidate_spec(ow_pool* p) {
     if (p->stream_trem) hipStreamSynchronize(p->stream_trem);
 }
 
-void free_stream_buffers(ow_pool* p) {
-    invalidate_spec(p);
-    if (p->d_sum) hipFree(p->d_sum);
-    if (p->d_rbuf) hipFree(p->d_rbuf);
-    if (p->d_pre) hipFree(p->d_pre);
-    if (p->d_out) hipFree(p->d_out);
-    p->d_sum = p->d_rbuf = p->d_pre = nullptr;
-    p->d_out = nullptr;
-}
-
+// Block buffers for `cap` samples.  The pool stands at capacity 0 from the moment the old ones are released until all the new ones exist:
+// a grow that fails leaves a pool whose next render grows again (len > Lcap) instead of launching on buffers that are gone.
 void alloc_stream_buffers(ow_pool* p, size_t cap) {
-    free_stream_buffers(p);
+    invalidate_spec(p);
+    p->Lcap = 0;
+    p->d_sum.reset(); p->d_rbuf.reset(); p->d_pre.reset(); p->d_out.reset();
     const size_t I = p->I;
-    HIP_OK(hipMalloc(&p->d_sum, sizeof(double) * 2 * I * cap));
-    HIP_OK(hipMalloc(&p->d_rbuf, sizeof(double) * 2 * (2 * cap * I)));   // two halves (current block, block ahead)
-    HIP_OK(hipMalloc(&p->d_pre, sizeof(double) * 2 * cap * I));
-    HIP_OK(hipMalloc(&p->d_out, sizeof(float) * I * cap));
+    p->d_sum.alloc(2 * I * cap);
+    p->d_rbuf.alloc(2 * (2 * cap * I));   // two halves (current block, block ahead)
+    p->d_pre.alloc(2 * cap * I);
+    p->d_out.alloc(I * cap);
     HIP_OK(hipMemsetAsync(p->d_out, 0, sizeof(float) * I * cap, p->stream));
-    if (p->d_pa_tap) {      // the test tap follows the block capacity
-        hipFree(p->d_pa_tap); p->d_pa_tap = nullptr;
-        HIP_OK(hipMalloc(&p->d_pa_tap, sizeof(double) * 2 * cap * I));
-    }
+    if (p->d_pa_tap) p->d_pa_tap.alloc(2 * cap * I);      // the test tap follows the block capacity
     p->Lcap = cap;
 }
 
@@ -50,11 +41,9 @@ void alloc_stream_buffers(ow_pool* p, size_t cap) {
 void ensure_ops_capacity(ow_pool* p, size_t n) {
     if (n <= p->ops_cap) return;
     size_t cap = std::max<size_t>(n, std::max<size_t>(p->ops_cap * 2, 256));
-    if (p->d_ops) hipFree(p->d_ops);
-    if (p->h_ops) hipHostFree(p->h_ops);
-    p->d_ops = nullptr; p->h_ops = nullptr; p->ops_cap = 0;   // a failed allocation below must not leave freed pointers behind
-    HIP_OK(hipMalloc(&p->d_ops, sizeof(OwOp) * cap));
-    HIP_OK(hipHostMalloc(&p->h_ops, sizeof(OwOp) * cap));
+    p->ops_cap = 0;                        // until both exist: a failed allocation leaves a pool that grows again
+    p->d_ops.alloc(cap);
+    p->h_ops.alloc(cap);
     p->ops_cap = cap;
 }
 
@@ -154,3 +143,10 @@ TremSettled trem_settled_rows(int device, double os_sr, const OwConsts* dK, cons
     return t;
 }
 }  // namespace
+
+ow_pool::~ow_pool() {      // also of a pool that pool_create gave up half-way: whatever exists is drained, then the members release themselves
+    hipSetDevice(device);
+    if (stream) hipStreamSynchronize(stream);
+    invalidate_spec(this);
+    for (int k = 1; k < OW_MAX_STAGES; ++k) if (pipe_stream[k]) hipStreamSynchronize(pipe_stream[k]);
+}

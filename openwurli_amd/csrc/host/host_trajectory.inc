@@ -11,12 +11,13 @@ struct TremTraj {
     int device = 0;
     double os_sr = 0.0;
     std::mutex mu;                    // guards len / cap / buffers / marks / enqueues on `stream`; held for host-side enqueue work only
-    OwConsts* dK = nullptr;           // constants at the chain rate (the tremolo fields are all the kernels read)
-    double* d_r = nullptr;            // [cap + 64]
-    double* d_state = nullptr;        // [18] oscillator rows at sample `len`
+    StreamOwner stream;               // (first: released last, after the buffers and marks)
+    DevBuf<OwConsts> dK;              // constants at the chain rate (the tremolo fields are all the kernels read)
+    double* d_r = nullptr;            // [cap + 64]; plain, like d_ckpt: a growth swaps them and retires the old ones
+    DevBuf<double> d_state;           // [18] oscillator rows at sample `len`
     double* d_ckpt = nullptr;         // [cap / OW_TRAJ_CK + 2][OW_TRAJ_CKD]
-    unsigned long long* d_be = nullptr;   // [1 + OW_TRAJ_BE_CAP]
-    uint32_t* d_zero = nullptr;       // leaders = {0} for the settle kernels
+    DevBuf<unsigned long long> d_be;  // [1 + OW_TRAJ_BE_CAP]
+    DevBuf<uint32_t> d_zero;          // leaders = {0} for the settle kernels
     size_t cap = 0, len = 0;          // cap: samples the buffers hold; len: samples produced or enqueued for production
     size_t cap_max = 0;               // configured capacity (ow_tremolo_configure / OW_TREM_TRAJ_SECONDS): the buffers grow up to it, an engine
                                       // older than this leaves the store (trem_evict)
@@ -26,9 +27,8 @@ struct TremTraj {
     std::chrono::steady_clock::time_point reader_seen{};
     size_t done = 0;                  // samples known to be complete (a recorded mark was seen finished)
     uint64_t be_settle = 0;           // fallbacks the settle itself counted (what a fresh CircuitState carries after Tremolo::new)
-    hipStream_t stream = nullptr;
     static constexpr int NMARK = 16;
-    struct Mark { size_t end = 0; hipEvent_t ev = nullptr; } mark[NMARK];
+    struct Mark { size_t end = 0; Event ev; } mark[NMARK];
     int head = 0;
     bool grow_requested = false;      // the helper thread has been asked to double the buffers
     std::vector<void*> retired;       // buffers a growth replaced: kernels launched before the swap may still read them, so they are only
@@ -36,11 +36,8 @@ struct TremTraj {
     ~TremTraj() {
         hipSetDevice(device);
         if (stream) hipStreamSynchronize(stream);
-        for (auto& m : mark) if (m.ev) hipEventDestroy(m.ev);
-        if (dK) hipFree(dK); if (d_r) hipFree(d_r); if (d_state) hipFree(d_state); if (d_ckpt) hipFree(d_ckpt);
+        if (d_r) hipFree(d_r); if (d_ckpt) hipFree(d_ckpt);
         for (void* q : retired) hipFree(q);
-        if (d_be) hipFree(d_be); if (d_zero) hipFree(d_zero);
-        if (stream) hipStreamDestroy(stream);
     }
     static size_t ckpt_doubles(size_t c) { return (size_t)OW_TRAJ_CKD * (c / OW_TRAJ_CK + 2); }
     // Buffers for `new_cap` samples: allocate (no lock held: hipMalloc may take milliseconds), then under the lock copy what exists on the
@@ -64,8 +61,7 @@ struct TremTraj {
             HIP_OK(hipEventRecord(m.ev, stream));
             m.end = len;
             retired.push_back(d_r); retired.push_back(d_ckpt);
-            d_r = nr.as<double>(); d_ckpt = nc.as<double>(); cap = new_cap;
-            nr.p = nullptr; nc.p = nullptr;
+            d_r = (double*)nr.release(); d_ckpt = (double*)nc.release(); cap = new_cap;
             done = 0;                                      // everything has to be waited for again (the copy)
             for (Mark& o : mark) if (&o != &m && o.end <= len) o.end = 0;     // older marks stand for data in the old buffer
             grow_requested = false;
@@ -284,14 +280,15 @@ std::shared_ptr<TremTraj> traj_acquire(int device, const OwConsts& hc, const OwC
     t->lead = (size_t)std::min(lead * hc.os_sr, (double)t->cap_max);
     const size_t first = n_engines >= 4096 ? t->cap_max : std::min(t->cap_max, ((size_t)(OW_TRAJ_FIRST_SECONDS * hc.os_sr) + OW_TRAJ_CK - 1) / OW_TRAJ_CK * OW_TRAJ_CK);
     t->cap = first;
-    HIP_OK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
-    for (auto& m : t->mark) HIP_OK(hipEventCreateWithFlags(&m.ev, hipEventDisableTiming));
-    HIP_OK(hipMalloc(&t->dK, sizeof(OwConsts)));
-    HIP_OK(hipMalloc(&t->d_r, sizeof(double) * (t->cap + 64)));
-    HIP_OK(hipMalloc(&t->d_state, sizeof(double) * 18));
-    HIP_OK(hipMalloc(&t->d_ckpt, sizeof(double) * TremTraj::ckpt_doubles(t->cap)));
-    HIP_OK(hipMalloc(&t->d_be, sizeof(unsigned long long) * (1 + OW_TRAJ_BE_CAP)));
-    HIP_OK(hipMalloc(&t->d_zero, sizeof(uint32_t)));
+    t->stream.create();
+    for (auto& m : t->mark) m.ev.create();
+    DevMem r, ck;
+    t->dK.alloc(1);
+    r.alloc(sizeof(double) * (t->cap + 64)); t->d_r = (double*)r.release();
+    t->d_state.alloc(18);
+    ck.alloc(sizeof(double) * TremTraj::ckpt_doubles(t->cap)); t->d_ckpt = (double*)ck.release();
+    t->d_be.alloc(1 + OW_TRAJ_BE_CAP);
+    t->d_zero.alloc(1);
     HIP_OK(hipMemsetAsync(t->d_be, 0xFF, sizeof(unsigned long long) * (1 + OW_TRAJ_BE_CAP), t->stream));
     HIP_OK(hipMemsetAsync(t->d_be, 0, sizeof(unsigned long long), t->stream));
     HIP_OK(hipMemsetAsync(t->d_zero, 0, sizeof(uint32_t), t->stream));
