@@ -628,6 +628,49 @@ typedef struct ow_overshoot_row {
 long long ow_overshoot(const ow_note_job* jobs, size_t n_jobs, const ow_overshoot_cfg* cfg, ow_overshoot_row* rows_out, double* audio_out,
                        size_t audio_stride);
 
+/* ---- the pump measurements: `preamp-bench pump-sweep` / `pump-trace` / `pump-spike` / `pump-step` / `pump-sinusoid` (main.rs:2329-3063) ----
+ * These commands drive gen_preamp::process_sample directly on a CircuitState::default() of the melange 12-node preamp: no adapter, no
+ * settled state, no main - shadow difference, no thermal noise.  One point is one run of one such state. */
+enum { OW_PUMP_STATIC = 0,      /* the resistance stays at r_settle */
+       OW_PUMP_STEP = 1,        /* set_runtime_R_r_ldr(r_to) before capture sample 0 (pump-step) */
+       OW_PUMP_RAMP = 2,        /* r_settle + (r_to - r_settle) * (k / (capture - 1)) before capture sample k (pump-spike's slew, :2779-2783) */
+       OW_PUMP_LOGCOS = 3 };    /* exp(ln_mid + ln_amp * cos((2 pi sched_freq) * (k * (1 / sample_rate)))) before sample k (pump-sinusoid, :2964-2998) */
+typedef struct ow_pump_point {
+    double sample_rate;          /* set_sample_rate(sample_rate) when it differs from 48 000 by more than 0.5; the codegen tables otherwise */
+    double r_settle;             /* set_runtime_R_r_ldr(r_settle) before the first sample (its clamp to 1 k..1 M and its 1e-12 hysteresis apply) */
+    uint64_t settle, capture;    /* sample counts */
+    double in_amp, in_freq;      /* input in_amp * sin((2 pi in_freq / sample_rate) * k), k counted from the first settle sample (the extra
+                                  * sample is not counted); in_amp == 0: silence */
+    uint32_t extra_sample;       /* 1: one more zero-input sample between settle and capture (pump-step's `settled`, the `prev` of the slew
+                                  * and of pump-sinusoid); its value is ow_pump_row.extra */
+    uint32_t schedule;           /* OW_PUMP_* */
+    double r_to;                 /* STEP, RAMP */
+    double ln_mid, ln_amp, sched_freq;   /* LOGCOS */
+} ow_pump_point;
+typedef struct ow_pump_cfg {
+    uint32_t struct_size;  /* = sizeof(ow_pump_cfg) of the caller's header */
+    uint32_t point_size;   /* = sizeof(ow_pump_point) of the caller's header (the stride of `points`) */
+    int device;
+    int reserved[5];
+} ow_pump_cfg;
+typedef struct ow_pump_row {
+    double sum, sum_sq;                       /* over the capture, in sample order (pump-sweep, :2397-2411) */
+    double mean, std, min, max;               /* sum / n, sqrt(max(sum_sq / n - mean^2, 0)), :2412-2414 */
+    double pair_mean, pair_std, raw_std;      /* pump-spike's measure (:2601-2619); meaningful when capture is even */
+    double extra;                             /* the extra sample's value (0 without one) */
+    double max_step;                          /* max |y[k] - y[k-1]| over the capture, y[-1] = the extra sample (without one: from k = 1) */
+    uint64_t nr_exhausted, be_fallbacks, voltage_damps, nan_resets;   /* the state's diag_* counters after the last sample */
+} ow_pump_row;
+/* Runs n points, every one on its own lane of the device, one launch per distinct sample rate (and per chunk of a fixed device-memory
+ * budget; OW_PUMP_CHUNK=<points> caps a chunk; tests use it).  rows_out: [n], in the caller's order.  trace_out: NULL, or host f64
+ * [n][trace_stride >= the largest capture] receiving every captured sample (a row's tail beyond its own capture is 0); asking for it
+ * changes no number.  A point's numbers do not depend on the other points of the call or on the chunking.  n == 0 returns 0 and touches
+ * nothing.
+ * Returns 0, <0 on error.  Refused before any device work (ow_last_error says why): "ABI mismatch", a non-finite or non-positive
+ * sample_rate / r_settle (and r_to, ln_amp's exp, sched_freq where the schedule uses them), a non-finite in_amp / in_freq, capture == 0,
+ * capture < 2 with OW_PUMP_RAMP, an unknown schedule, an extra_sample other than 0 or 1, a run of 2^40 samples or more, a short trace_stride, null arguments. */
+int ow_pump_measure(const ow_pump_point* points, size_t n, const ow_pump_cfg* cfg, ow_pump_row* rows_out, double* trace_out, size_t trace_stride);
+
 #ifdef __cplusplus
 }
 #endif

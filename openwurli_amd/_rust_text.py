@@ -42,3 +42,15 @@ def _f(x, spec):
     if math.isnan(x):
         return ("%" + spec.split(".")[0].lstrip("+") + "s") % "NaN"
     return ("%" + spec) % x
+
+
+def _e(x, prec, plus=False):
+    """Rust's {:.<prec>e} ({:+.<prec>e} with plus): the exponent carries neither padding nor a plus sign -- 1.000000e3, 8.540763e0,
+    2.5e-7 -- where Python prints 1.000000e+03.  NaN and inf as in _f."""
+    x = float(x)
+    if math.isnan(x):
+        return "NaN"
+    if math.isinf(x):
+        return ("+" if plus and x > 0 else "") + ("inf" if x > 0 else "-inf")
+    mant, exp = ((("%+." if plus else "%.") + str(int(prec)) + "e") % x).split("e")
+    return mant + "e" + str(int(exp))

@@ -224,6 +224,27 @@ class OwOvershootRow(C.Structure):
     _fields_ = [("note", C.c_uint8), ("velocity", C.c_uint8), ("reserved", C.c_uint8 * 6)] + [(f, C.c_double) for f in OVERSHOOT_ROW_FIELDS]
 
 
+PUMP_STATIC, PUMP_STEP, PUMP_RAMP, PUMP_LOGCOS = 0, 1, 2, 3                     # include/openwurli_hip.h OW_PUMP_*
+
+
+class OwPumpPoint(C.Structure):
+    _fields_ = [("sample_rate", C.c_double), ("r_settle", C.c_double), ("settle", C.c_uint64), ("capture", C.c_uint64), ("in_amp", C.c_double),
+                ("in_freq", C.c_double), ("extra_sample", C.c_uint32), ("schedule", C.c_uint32), ("r_to", C.c_double), ("ln_mid", C.c_double),
+                ("ln_amp", C.c_double), ("sched_freq", C.c_double)]
+
+
+class OwPumpCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("point_size", C.c_uint32), ("device", C.c_int), ("reserved", C.c_int * 5)]
+
+    def __init__(self, device=0):
+        super().__init__(C.sizeof(OwPumpCfg), C.sizeof(OwPumpPoint), device)
+
+
+class OwPumpRow(C.Structure):
+    _fields_ = [(f, C.c_double) for f in ("sum", "sum_sq", "mean", "std", "min", "max", "pair_mean", "pair_std", "raw_std", "extra", "max_step")] + \
+               [(f, C.c_uint64) for f in ("nr_exhausted", "be_fallbacks", "voltage_damps", "nan_resets")]
+
+
 # every symbol include/openwurli_hip.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 class OwSegment(C.Structure):
@@ -314,6 +335,7 @@ SYMBOLS = {
     "ow_intermod_probes": (C.c_int, [C.c_uint8, _VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ow_intermod_audit": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwIntermodCfg), _VP, _VP, C.c_size_t]),
     "ow_overshoot": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwOvershootCfg), _VP, _VP, C.c_size_t]),
+    "ow_pump_measure": (C.c_int, [_VP, C.c_size_t, C.POINTER(OwPumpCfg), _VP, _VP, C.c_size_t]),
 }
 
 

@@ -222,6 +222,7 @@ struct Switches {
     long long poly_chunk = 0;                  // OW_POLY_CHUNK=n: at most n chords per chunk of ow_render_poly (tests); 0: the device-memory budget alone
     long long centroid_chunk = 0;              // OW_CENTROID_CHUNK=n: at most n jobs per chunk of ow_centroid_track (tests); 0: the device-memory budget alone
     long long note_audit_chunk = 0;            // OW_NOTE_AUDIT_CHUNK=n: at most n jobs per chunk of ow_intermod_audit / ow_overshoot (tests); 0: the device-memory budget alone
+    long long pump_chunk = 0;                  // OW_PUMP_CHUNK=n: at most n points per launch of ow_pump_measure (tests); 0: the device-memory budget alone
     int pbench_row = -1;                       // OW_PBENCH_ROW=0/1: force the lane-pair / row kernel of ow_preamp_measure (legacy); -1: by grid size
     static int flag(const char* name, int dflt) { const char* e = std::getenv(name); return (e && e[0]) ? (e[0] - '0') : dflt; }
     static Switches from_env() {
@@ -258,6 +259,7 @@ struct Switches {
         if (const char* e = std::getenv("OW_POLY_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.poly_chunk = v; }
         if (const char* e = std::getenv("OW_CENTROID_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.centroid_chunk = v; }
         if (const char* e = std::getenv("OW_NOTE_AUDIT_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.note_audit_chunk = v; }
+        if (const char* e = std::getenv("OW_PUMP_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.pump_chunk = v; }
         w.pbench_row = flag("OW_PBENCH_ROW", -1); if (w.pbench_row > 1 || w.pbench_row < -1) w.pbench_row = -1;
         return w;
     }

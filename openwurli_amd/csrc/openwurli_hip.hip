@@ -40,6 +40,7 @@
 #include "ow_poly_kernels.h"
 #include "ow_centroid_kernels.h"
 #include "ow_note_audit_kernels.h"
+#include "ow_pump_kernels.h"
 #include "ow_midi_kernels.h"
 #include "ow_chain_wide.h"
 #include "ow_chain_stream.h"
@@ -71,3 +72,4 @@ using owdev::OwEngineOut;
 #include "host/api_render_poly.inc"     // C-ABI: `preamp-bench render-poly` (chord intermodulation, many chords per call)
 #include "host/api_centroid.inc"        // C-ABI: `preamp-bench centroid-track` (spectral centroid over time, many notes per call)
 #include "host/api_note_audit.inc"      // C-ABI: `preamp-bench intermod-audit` / `overshoot` (the note audits, many notes per call)
+#include "host/api_pump.inc"            // C-ABI: `preamp-bench pump-sweep` / `pump-trace` / `pump-spike` / `pump-step` / `pump-sinusoid` (the pump measurements)
