@@ -175,11 +175,20 @@ int ow_test_host_melange_paths(double rate);
 
 /* ---- latched switches ------------------------------------------------------------------------- */
 /* The OW_* environment switches ("Environment switches") are read once, when a pool is created, and kept in the pool: the
- * render path never calls getenv.  These change / read one on a live pool: "trem_serial", "trem_wide", "preamp_wide" (-1 = by size),
- * "mel_generic", "mel_rank1", "mel_lds", "pa_sort" (0..2), "host_profile"; get also answers "trem_traj" and "trem_cache".  set returns
- * 0, <0 for an unknown or creation-only switch; get returns the value, -2 for an unknown name. */
+ * render path never calls getenv.  These change / read one on a live pool, by its name in the library's one table of switches
+ * (host_base.inc: the variable's name in lower case without "OW_"; -1 = by size for the tri-state ones, "pa_sort" 0..2).  set returns 0,
+ * <0 for an unknown switch or one that is environment-only ("trem_traj", "trem_cache", the offline entry points' switches); get returns
+ * the value, -2 for an unknown name, and also answers "trem_traj" (the pool reads the shared trajectory), "voice_skew_active",
+ * "blocks_steady" / "_general" / "_attack" / "_steal" and "midi_device_bursts". */
 int ow_test_pool_set_switch(ow_pool*, const char* name, int value);
 int ow_test_pool_get_switch(const ow_pool*, const char* name);
+/* The chain and output-stage kernels one block of a pool gets (host only, no pool): preamp / power-amp kind of openwurli_hip.h, whether
+ * the chain is oversampled, whether the melange factors have the compiled-in sparsity pattern, engines and samples of the block,
+ * whether its rows go to a pinned block of ow_host_alloc.  switches: overrides of the DEFAULT switches (the environment is not read)
+ * as "name=value,name=value", or NULL.  Writes the kernels' names as a kernel trace shows them, e.g. "k_preamp_pair + k_post<false,true>"
+ * or "k_chain_stream" alone.  Returns 0; -1 for an unknown switch name, a refused value or a buffer that is too short. */
+int ow_test_block_plan(int preamp_kind, int power_amp_kind, int oversample, int ml_sparse_ok, int n_engines, int block_len, int to_pinned_block,
+                       const char* switches, char* out, size_t cap);
 /* out[0] = engines of the pool reading the shared tremolo trajectory, out[1] = samples its store holds (produced or enqueued),
  * out[2] = the store's capacity in samples. */
 int ow_test_pool_trajectory_info(const ow_pool*, uint64_t out[3]);

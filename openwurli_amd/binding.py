@@ -367,6 +367,7 @@ TEST_SYMBOLS = {
     "ow_test_clear_settle_caches": (C.c_int, []),
     "ow_test_pool_set_switch": (C.c_int, [_VP, C.c_char_p, C.c_int]),
     "ow_test_pool_get_switch": (C.c_int, [_VP, C.c_char_p]),
+    "ow_test_block_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t]),
     "ow_test_pool_trajectory_info": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     "ow_test_pool_trajectory_state": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     "ow_test_host_melange_paths": (C.c_int, [C.c_double]),

@@ -218,7 +218,7 @@ static bool midi_burst_on_device(ow_pool* p, const ow_midi_event* ev, size_t n) 
     // of a whole-pool re-strike's k_apply_ops now cover the download and the host's packing, scanning and list building for the block
     // that follows.  Ops the host had queued before the burst keep it off this path altogether (above); ops it queues afterwards are
     // applied by the next render, behind these, as before.
-    hipStream_t sc = p->pipe_stream[1] ? p->pipe_stream[1] : st;
+    hipStream_t sc = p->stream_copy ? p->stream_copy : st;
     if (sc != st) HIP_OK(hipStreamWaitEvent(sc, p->ev_vm_events, 0));
     HIP_OK(hipMemcpyAsync(p->h_vm + e_lo, p->d_vm + e_lo, sizeof(OwVm) * (e_hi - e_lo), hipMemcpyDeviceToHost, sc));
     HIP_OK(hipEventRecord(p->ev_vm, sc));

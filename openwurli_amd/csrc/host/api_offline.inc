@@ -80,7 +80,7 @@ long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg*
         const JobChainCfg cc{cfg->sample_rate, cfg->device, cfg->preamp_kind, cfg->power_amp_kind, cfg->no_rail_sag};
         // Voices and chain side by side when the chain is the plain legacy one and leaves room on the chip: a job's run time is serial
         // latency in both kernels, so the 13 % the voices take are hidden behind the chain instead of in front of it.
-        const bool overlap = job_chain_is_plain_legacy(cc, hj) && job_voice_overlap(n_jobs);
+        const bool overlap = job_chain_is_plain_legacy(cc, hj) && job_voice_overlap(call.sw, n_jobs);
         DevMem m_prog;
         StreamOwner so2;
         Event ev_ready, ev_voice;

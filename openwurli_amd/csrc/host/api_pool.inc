@@ -80,11 +80,11 @@ void ow_pool_render(ow_pool* p, float* out_host, size_t out_stride, size_t len) 
         post_render_host(p, 0, (int)p->I, len);
         auto t3 = std::chrono::steady_clock::now();
         collect_profile(p);
-        if (p->d_vm && p->vm_bursts && p->vm_host_dirty && p->pipe_stream[1] && !p->vm_download_pending) {   // see ow_pool::ev_vm_up
-            if (p->vm_upload_inflight) HIP_OK(hipStreamWaitEvent(p->pipe_stream[1], p->ev_vm_up, 0));
+        if (p->d_vm && p->vm_bursts && p->vm_host_dirty && p->stream_copy && !p->vm_download_pending) {   // see ow_pool::ev_vm_up
+            if (p->vm_upload_inflight) HIP_OK(hipStreamWaitEvent(p->stream_copy, p->ev_vm_up, 0));
             __atomic_store_n(&p->vm_host_dirty, (uint8_t)0, __ATOMIC_RELAXED);
-            HIP_OK(hipMemcpyAsync(p->d_vm, p->h_vm, sizeof(OwVm) * p->I, hipMemcpyHostToDevice, p->pipe_stream[1]));
-            HIP_OK(hipEventRecord(p->ev_vm_up, p->pipe_stream[1]));
+            HIP_OK(hipMemcpyAsync(p->d_vm, p->h_vm, sizeof(OwVm) * p->I, hipMemcpyHostToDevice, p->stream_copy));
+            HIP_OK(hipEventRecord(p->ev_vm_up, p->stream_copy));
             p->vm_upload_inflight = true;
         }
         auto t4 = std::chrono::steady_clock::now();
@@ -104,7 +104,7 @@ void ow_pool_render(ow_pool* p, float* out_host, size_t out_stride, size_t len) 
         p->args_stale = true; p->lists_valid = false; p->steal_counted = false;
         // "never fails, degrades to silence" (SURVEY 8b; engine.rs:450-458 does the same for numeric failure): every row of the
         // caller's block is written.  Drain the stream first so that an output copy already queued cannot land after the zeros.
-        for (int k = 0; k < OW_MAX_STAGES; ++k) if (p->pipe_stream[k]) hipStreamSynchronize(p->pipe_stream[k]);
+        for (hipStream_t s : {(hipStream_t)p->stream, (hipStream_t)p->stream_trem, (hipStream_t)p->stream_copy}) if (s) hipStreamSynchronize(s);
         if (out_host && out_stride >= len)
             for (size_t e = 0; e < p->I; ++e) std::memset(out_host + e * out_stride, 0, len * sizeof(float));
         if (p->d_out && len <= p->Lcap) { hipMemset(p->d_out, 0, sizeof(float) * len * p->I); p->out_ld = len; }   // the HBM copy of the block too

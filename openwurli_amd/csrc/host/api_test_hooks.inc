@@ -315,67 +315,44 @@ int ow_test_pool_set_switch(ow_pool* p, const char* name, int value) {
     if (hipSetDevice(p->device) != hipSuccess) return -1;
     invalidate_spec(p);                                   // a pending block-ahead result was produced under the old schedule
     if (hipStreamSynchronize(p->stream) != hipSuccess) return -1;
-    Switches& w = p->sw;
-    if (n == "trem_serial") w.trem_serial = value != 0;
-    else if (n == "trem_wide") w.trem_wide = value < 0 ? -1 : (value != 0);
-    else if (n == "preamp_wide") w.preamp_wide = value < 0 ? -1 : (value != 0);
-    else if (n == "chain_fused") w.chain_fused = value < 0 ? -1 : (value != 0);
-    else if (n == "mel_generic") w.mel_generic = value != 0;
-    else if (n == "mel_rank1") w.mel_rank1 = value != 0;
-    else if (n == "mel_lds") w.mel_lds = value != 0;
-    else if (n == "mel_eng") w.mel_eng = value != 0;
-    else if (n == "eout_attn") w.eout_attn = value < 0 ? -1 : (value != 0);
-    else if (n == "voice_skew") w.voice_skew = value != 0;
-    else if (n == "pa_sort") { if (value < 0 || value > 2) return -1; w.pa_sort = value; }
-    else if (n == "host_profile") w.host_profile = value != 0;
-    else if (n == "out_direct") w.out_direct = value < 0 ? -1 : (value != 0);
-    else if (n == "midi_device") w.midi_device = value < 0 ? -1 : (value != 0);
-    else if (n == "voice_attack") { w.voice_attack = value != 0; p->lists_valid = false; }
-    else if (n == "voice_steal") w.voice_steal = value != 0;
-    else if (n == "voice_release") w.voice_release = value != 0;
-    else if (n == "midi_apply_early") w.midi_apply_early = value != 0;
-    else if (n == "force_general") { w.force_general = value != 0; p->lists_valid = false; }
-    else if (n == "chain_stream") w.chain_stream = value < 0 ? -1 : (value != 0);
-    else if (n == "chain_row") w.chain_row = value < 0 ? -1 : (value != 0);
-    else if (n == "post_pair") w.post_pair = value < 0 ? -1 : (value != 0);
-    else if (n == "preamp_pair") w.preamp_pair = value < 0 ? -1 : (value != 0);
-    else return -1;                                       // (trem_traj / trem_cache / pipe shape the pool at creation: environment only)
+    if (!p->sw.set(name, value)) return -1;               // (trem_traj / trem_cache shape the pool at creation: environment only)
+    if (n == "voice_attack" || n == "force_general") p->lists_valid = false;
     return 0;
 }
 int ow_test_pool_get_switch(const ow_pool* p, const char* name) {
     if (!p || !name) return -2;
     const std::string n(name);
-    const Switches& w = p->sw;
-    if (n == "trem_serial") return w.trem_serial;
-    if (n == "trem_wide") return w.trem_wide;
-    if (n == "preamp_wide") return w.preamp_wide;
-    if (n == "chain_fused") return w.chain_fused;
-    if (n == "chain_row") return w.chain_row;
-    if (n == "mel_generic") return w.mel_generic;
-    if (n == "mel_rank1") return w.mel_rank1;
-    if (n == "mel_lds") return w.mel_lds;
-    if (n == "mel_eng") return w.mel_eng;
-    if (n == "eout_attn") return w.eout_attn;
-    if (n == "voice_skew") return w.voice_skew;
+    // read-only pseudo-names first: what the pool is doing, not what a switch says
     if (n == "voice_skew_active") return p->skew_next ? 1 : 0;   // the next steady launch takes the skewed variant
-    if (n == "pa_sort") return w.pa_sort;
     if (n == "trem_traj") return p->traj ? 1 : 0;
-    if (n == "trem_cache") return w.trem_cache;
-    if (n == "out_direct") return w.out_direct;
-    if (n == "midi_device") return w.midi_device;
-    if (n == "voice_attack") return w.voice_attack;
-    if (n == "voice_steal") return w.voice_steal;
-    if (n == "voice_release") return w.voice_release;
-    if (n == "midi_apply_early") return w.midi_apply_early;
     if (n == "blocks_steady") return (int)p->vl_steady.n_blocks;   // wavefront blocks of the voice lists the last render launched
     if (n == "blocks_general") return (int)p->vl_general.n_blocks;
     if (n == "blocks_attack") return (int)p->vl_attack.n_blocks;
     if (n == "blocks_steal") return (int)p->vl_steal.n_blocks;
     if (n == "midi_device_bursts") return (int)std::min<uint64_t>(p->vm_bursts, 0x7FFFFFFF);
-    if (n == "chain_stream") return w.chain_stream;
-    if (n == "post_pair") return w.post_pair;
-    if (n == "preamp_pair") return w.preamp_pair;
-    return -2;
+    int v = 0;
+    return p->sw.get(name, &v) ? v : -2;
+}
+// Which chain and output-stage kernels a block of such a pool gets (choose_chain / choose_post, host_pool.inc): host only, no pool.
+int ow_test_block_plan(int preamp_kind, int power_amp_kind, int oversample, int ml_sparse_ok, int n_engines, int block_len, int to_pinned_block,
+                       const char* switches, char* out, size_t cap) {
+    if (!out) return -1;
+    Switches sw;                                           // the defaults, not the environment
+    for (const char* s = switches; s && *s;) {             // "name=value,name=value"
+        const char* eq = std::strchr(s, '=');
+        if (!eq) return -1;
+        char* end = nullptr;
+        const long v = std::strtol(eq + 1, &end, 10);
+        if (end == eq + 1 || (*end && *end != ',')) return -1;
+        if (!sw.set(std::string(s, eq).c_str(), (int)v)) return -1;
+        s = *end ? end + 1 : end;
+    }
+    const ChainKernel chain = choose_chain(sw, preamp_kind, power_amp_kind, oversample != 0, ml_sparse_ok != 0, n_engines, block_len, to_pinned_block != 0);
+    const PostKernel post = choose_post(sw, power_amp_kind, oversample != 0, n_engines, chain);
+    const std::string plan = std::string(CHAIN_KERNEL_NAME[chain]) + (post != POST_NONE ? " + " : "") + POST_KERNEL_NAME[post];
+    if (plan.size() + 1 > cap) return -1;
+    std::memcpy(out, plan.c_str(), plan.size() + 1);
+    return 0;
 }
 // Engines of the pool that read the shared trajectory / samples the store of the pool's rate holds (produced or enqueued) / its capacity.
 int ow_test_pool_trajectory_info(const ow_pool* p, uint64_t out[3]) {

@@ -173,7 +173,6 @@ class Workers {
     static thread_local bool in_slice_;
 };
 thread_local bool Workers::in_slice_ = false;
-#define OW_MAX_STAGES 8
 #define OW_MAX_SLICES 64   // upper bound of the slices one dispatch is cut into (scratch arrays live on the stack)
 
 struct HostSmoother {  // host mirror of LinearSmoother::target only (the 1e-9 acceptance test, engine.rs:86-89)
@@ -189,79 +188,89 @@ struct HostSmoother {  // host mirror of LinearSmoother::target only (the 1e-9 a
 };
 
 // Measurement and test switches.  Every OW_* environment variable that selects between kernel paths is read ONCE, when a pool is
-// created (std::getenv is neither realtime-safe nor safe against a concurrent setenv in the host), and kept in the pool; the render
-// path only looks at the latched copy.  ow_test_pool_set_switch (openwurli_hip_test.h) changes one on a live pool.
+// created or an offline entry point is called (std::getenv is neither realtime-safe nor safe against a concurrent setenv in the host),
+// and kept there; the render path only looks at the latched copy.  ow_test_pool_set_switch (openwurli_hip_test.h) changes one on a live pool.
+// Kinds, and what a switch takes from its environment variable (by the first character, Switches::flag's rule; SW_COUNT: the whole number;
+// anything outside lo..hi leaves the default) and from set():
+//   SW_BOOL 0 / 1 (set: value != 0)   SW_TRI -1 = by size / 0 / 1 (set: negative -> -1, else value != 0)   SW_RANGE, SW_COUNT lo..hi (set refuses the rest)
+enum SwitchKind { SW_BOOL, SW_TRI, SW_RANGE, SW_COUNT };
+static bool switch_from_env(const char* env, SwitchKind kind, long long lo, long long hi, long long* v) {
+    const char* e = env ? std::getenv(env) : nullptr;
+    if (!e || !e[0]) return false;
+    *v = kind == SW_COUNT ? std::atoll(e) : (long long)(e[0] - '0');
+    return *v >= lo && *v <= hi;
+}
+static bool switch_from_set(SwitchKind kind, long long lo, long long hi, long long* v) {
+    if (kind == SW_BOOL) *v = *v != 0;
+    else if (kind == SW_TRI) *v = *v < 0 ? -1 : (*v != 0);
+    return *v >= lo && *v <= hi;
+}
+// THE table of switches, one row each: member type, name (the member; what the test hooks and ow_test_block_plan call it), default,
+// environment variable (nullptr: none), kind, lo, hi, settable (false: it shapes a pool at creation or belongs to the offline entry
+// points -- environment only).  Everything below the table is generated from it.
+#define OW_SWITCH_TABLE(X) \
+    X(int, trem_wide, -1, "OW_TREM_WIDE", SW_TRI, -1, 1, true)                         /* -1: by pool size */ \
+    X(int, preamp_wide, -1, "OW_PREAMP_WIDE", SW_TRI, -1, 1, true)                     /* -1: by pool size */ \
+    X(int, chain_fused, -1, "OW_CHAIN_FUSED", SW_TRI, -1, 1, true)                     /* preamp + output stage as one launch (k_chain_fused); -1: whenever the quad preamp is used */ \
+    X(bool, trem_serial, false, "OW_TREM_SERIAL", SW_BOOL, 0, 1, true)                 /* 1: block-ahead oscillators in front of the voices instead of beside them */ \
+    X(bool, trem_cache, true, "OW_TREM_CACHE", SW_BOOL, 0, 1, false)                   /* 0: no process-wide settled-state cache */ \
+    X(bool, trem_traj, true, "OW_TREM_TRAJ", SW_BOOL, 0, 1, false)                     /* 0: no shared trajectory, one oscillator per phase group (rounds 1-3) */ \
+    X(bool, mel_rank1, false, "OW_MEL_RANK1", SW_BOOL, 0, 1, true)                     /* the melange preamp kernels: see choose_chain */ \
+    X(bool, mel_lds, false, "OW_MEL_LDS", SW_BOOL, 0, 1, true)                         \
+    X(bool, mel_generic, false, "OW_MEL_GENERIC", SW_BOOL, 0, 1, true)                 \
+    X(int, mel_eng, 0, "OW_MEL_ENG", SW_BOOL, 0, 1, true)                              /* 1: lane = engine melange kernel (k_preamp_mel_eng; measured -3 % at 131 072 engines, 2x slower at 65 536) */ \
+    X(bool, voice_skew, true, "OW_VOICE_SKEW", SW_BOOL, 0, 1, true)                    /* 0: the steady voice kernel without skewed lane clocks (one jitter grid per wavefront assumed) */ \
+    X(int, pa_sort, 1, "OW_PA_SORT", SW_RANGE, 0, 2, true)                             /* 0 never, 1 when the block exceeds the chip, 2 always */ \
+    X(int, eout_attn, -1, "OW_EOUT_ATTN", SW_TRI, -1, 1, true)                         /* status summary instead of the status blocks (k_eout_attention); -1: ranges of >= 8 192 engines */ \
+    X(int, midi_device, -1, "OW_MIDI_DEVICE", SW_TRI, -1, 1, true)                     /* bursts of ow_pool_midi applied on the device (k_vm_events) never / whenever the list allows; -1: pools of >= 8 192 engines, >= 65 536 events */ \
+    X(int, midi_apply_early, 1, "OW_MIDI_APPLY_EARLY", SW_BOOL, 0, 1, true)            /* 0: the queues of a device burst wait for the next render's k_apply_ops */ \
+    X(int, voice_release, 1, "OW_VOICE_RELEASE", SW_BOOL, 0, 1, true)                  /* 0: no release variant of the steady voice kernel (k_voice renders every engine with a damping voice) */ \
+    X(int, voice_steal, 1, "OW_VOICE_STEAL", SW_BOOL, 0, 1, true)                      /* 0: no steal variant of the steady voice kernel (k_voice renders every crossfade) */ \
+    X(int, voice_attack, 1, "OW_VOICE_ATTACK", SW_BOOL, 0, 1, true)                    /* 0: no attack variant of the steady voice kernel (engines in onset / noise phases go to the general kernel) */ \
+    X(bool, force_general, false, nullptr, SW_BOOL, 0, 1, true)                        /* test / probe hook: every engine's slot voices go to the general voice kernel (what it costs without any phase active) */ \
+    X(int, chain_row, -1, "OW_CHAIN_ROW", SW_TRI, -1, 1, true)                         /* the fused chain launch with one solver state per row of sixteen lanes (k_chain_row) never / whenever the chain is fused; -1: ranges of <= 1 024 engines */ \
+    X(int, chain_stream, -1, "OW_CHAIN_STREAM", SW_TRI, -1, 1, true)                   /* preamp + output stage of a big oversampled pool as one launch (k_chain_stream); -1: when the block goes to a pinned host block */ \
+    X(int, post_pair, -1, "OW_POST_PAIR", SW_TRI, -1, 1, true)                         /* the oversampled output stage with lane = engine (k_post<false, true>) never / always; -1: ranges of >= 131 072 engines (two wavefronts per SIMD without the lane pair) */ \
+    X(int, preamp_pair, -1, "OW_PREAMP_PAIR", SW_TRI, -1, 1, true)                     /* the legacy preamp on the lane path with lane = engine, main and shadow state in one lane (k_preamp_pair) never / always; -1: ranges of >= 131 072 engines */ \
+    X(int, out_direct, -1, "OW_OUT_DIRECT", SW_TRI, -1, 1, true)                       /* output stage stores straight into a pinned host block (ow_host_alloc) instead of d_out + copy; -1: default */ \
+    X(bool, host_profile, false, "OW_HOST_PROFILE", SW_BOOL, 0, 1, true)               /* 1: ow_pool_render prints launch / wait / post of every slow block */ \
+    X(int, midi_threads, 0, "OW_MIDI_THREADS", SW_COUNT, 1, 64, false)                 \
+    X(long long, calib_chunk, 0, "OW_CALIB_CHUNK", SW_COUNT, 1, LLONG_MAX, false)      /* at most n points per chunk of ow_calibrate (tests); 0: the device-memory budget alone */ \
+    X(long long, pbench_chunk, 0, "OW_PBENCH_CHUNK", SW_COUNT, 1, LLONG_MAX, false)    /* at most n points per launch of ow_preamp_measure (tests); 0: one launch, or the trace budget */ \
+    X(long long, poly_chunk, 0, "OW_POLY_CHUNK", SW_COUNT, 1, LLONG_MAX, false)        /* at most n chords per chunk of ow_render_poly (tests); 0: the device-memory budget alone */ \
+    X(long long, centroid_chunk, 0, "OW_CENTROID_CHUNK", SW_COUNT, 1, LLONG_MAX, false) /* at most n jobs per chunk of ow_centroid_track (tests); 0: the device-memory budget alone */ \
+    X(long long, note_audit_chunk, 0, "OW_NOTE_AUDIT_CHUNK", SW_COUNT, 1, LLONG_MAX, false) /* at most n jobs per chunk of ow_intermod_audit / ow_overshoot (tests); 0: the device-memory budget alone */ \
+    X(long long, pump_chunk, 0, "OW_PUMP_CHUNK", SW_COUNT, 1, LLONG_MAX, false)        /* at most n points per launch of ow_pump_measure (tests); 0: the device-memory budget alone */ \
+    X(int, pbench_row, -1, "OW_PBENCH_ROW", SW_TRI, -1, 1, false)                      /* force the lane-pair / row kernel of ow_preamp_measure (legacy); -1: by grid size */ \
+    X(int, chain_wide, -1, "OW_CHAIN_WIDE", SW_TRI, -1, 1, false)                      /* job paths (host_jobs_chain.inc): a quad of lanes per preamp state never / always; -1: up to 8 192 jobs */ \
+    X(int, job_fused, -1, "OW_JOB_FUSED", SW_TRI, -1, 1, false)                        /* ... as preamp | output stage on two wavefronts (k_job_chain_fused) never / always; -1: up to 4 096 jobs */ \
+    X(bool, job_overlap, true, "OW_JOB_OVERLAP", SW_BOOL, 0, 1, false)                 /* 0: the batch render's voices in front of the fused chain instead of beside it */ \
+    X(int, job_row, -1, "OW_JOB_ROW", SW_TRI, -1, 1, false)                            /* ... with a row of sixteen lanes per solver state (k_job_chain_row) never / always; -1: up to 1 024 jobs */
 struct Switches {
-    int trem_wide = -1, preamp_wide = -1;      // -1: by pool size
-    int chain_fused = -1;                      // OW_CHAIN_FUSED=0/1: preamp + output stage as one launch (k_chain_fused); -1: whenever the quad preamp is used
-    bool trem_serial = false;                  // OW_TREM_SERIAL=1: block-ahead oscillators in front of the voices instead of beside them
-    bool trem_cache = true;                    // OW_TREM_CACHE=0: no process-wide settled-state cache
-    bool trem_traj = true;                     // OW_TREM_TRAJ=0: no shared trajectory, one oscillator per phase group (rounds 1-3)
-    bool mel_rank1 = false, mel_lds = false, mel_generic = false;
-    int mel_eng = 0;                           // OW_MEL_ENG=1: lane = engine melange kernel (k_preamp_mel_eng; measured -3 % at 131 072 engines, 2x slower at 65 536)
-    bool voice_skew = true;                    // OW_VOICE_SKEW=0: the steady voice kernel without skewed lane clocks (one jitter grid per wavefront assumed)
-    int pa_sort = 1;                           // OW_PA_SORT: 0 never, 1 when the block exceeds the chip, 2 always
-    int eout_attn = -1;                        // OW_EOUT_ATTN=0/1: status summary instead of the status blocks (k_eout_attention); -1: ranges of >= 8 192 engines
-    int pipe = 0;                              // OW_PIPE=n stages
-    int midi_device = -1;                      // OW_MIDI_DEVICE=0/1: bursts of ow_pool_midi applied on the device (k_vm_events) never / whenever the list allows; -1: pools of >= 8 192 engines, >= 65 536 events
-    int midi_apply_early = 1;                  // OW_MIDI_APPLY_EARLY=0: the queues of a device burst wait for the next render's k_apply_ops
-    int voice_release = 1;                     // OW_VOICE_RELEASE=0: no release variant of the steady voice kernel (k_voice renders every engine with a damping voice)
-    int voice_steal = 1;                       // OW_VOICE_STEAL=0: no steal variant of the steady voice kernel (k_voice renders every crossfade)
-    int voice_attack = 1;                      // OW_VOICE_ATTACK=0: no attack variant of the steady voice kernel (engines in onset / noise phases go to the general kernel)
-    bool force_general = false;                // test / probe hook: every engine's slot voices go to the general voice kernel (what it costs without any phase active)
-    int chain_row = -1;                        // OW_CHAIN_ROW=0/1: the fused chain launch with one solver state per row of sixteen lanes (k_chain_row) never / whenever the chain is fused; -1: ranges of <= 1 024 engines
-    int chain_stream = -1;                     // OW_CHAIN_STREAM=0/1: preamp + output stage of a big oversampled pool as one launch (k_chain_stream); -1: when the block goes to a pinned host block
-    int post_pair = -1;                        // OW_POST_PAIR=0/1: the oversampled output stage with lane = engine (k_post<false, true>) never / always; -1: ranges of >= 131 072 engines (two wavefronts per SIMD without the lane pair)
-    int preamp_pair = -1;                      // OW_PREAMP_PAIR=0/1: the legacy preamp on the lane path with lane = engine, main and shadow state in one lane (k_preamp_pair) never / always; -1: ranges of >= 131 072 engines
-    int out_direct = -1;                       // OW_OUT_DIRECT=0/1: output stage stores straight into a pinned host block (ow_host_alloc) instead of d_out + copy; -1: default
-    bool pipe_overlap = false;
-    bool host_profile = false;
-    int midi_threads = 0;                      // OW_MIDI_THREADS
-    long long calib_chunk = 0;                 // OW_CALIB_CHUNK=n: at most n points per chunk of ow_calibrate (tests); 0: the device-memory budget alone
-    long long pbench_chunk = 0;                // OW_PBENCH_CHUNK=n: at most n points per launch of ow_preamp_measure (tests); 0: one launch, or the trace budget
-    long long poly_chunk = 0;                  // OW_POLY_CHUNK=n: at most n chords per chunk of ow_render_poly (tests); 0: the device-memory budget alone
-    long long centroid_chunk = 0;              // OW_CENTROID_CHUNK=n: at most n jobs per chunk of ow_centroid_track (tests); 0: the device-memory budget alone
-    long long note_audit_chunk = 0;            // OW_NOTE_AUDIT_CHUNK=n: at most n jobs per chunk of ow_intermod_audit / ow_overshoot (tests); 0: the device-memory budget alone
-    long long pump_chunk = 0;                  // OW_PUMP_CHUNK=n: at most n points per launch of ow_pump_measure (tests); 0: the device-memory budget alone
-    int pbench_row = -1;                       // OW_PBENCH_ROW=0/1: force the lane-pair / row kernel of ow_preamp_measure (legacy); -1: by grid size
+#define X(type, name, dflt, env, kind, lo, hi, settable) type name = dflt;
+    OW_SWITCH_TABLE(X)
+#undef X
     static int flag(const char* name, int dflt) { const char* e = std::getenv(name); return (e && e[0]) ? (e[0] - '0') : dflt; }
     static Switches from_env() {
         Switches w;
-        w.trem_wide = flag("OW_TREM_WIDE", -1); w.preamp_wide = flag("OW_PREAMP_WIDE", -1);
-        if (w.trem_wide > 1 || w.trem_wide < -1) w.trem_wide = -1;
-        if (w.preamp_wide > 1 || w.preamp_wide < -1) w.preamp_wide = -1;
-        w.chain_fused = flag("OW_CHAIN_FUSED", -1);
-        if (w.chain_fused > 1 || w.chain_fused < -1) w.chain_fused = -1;
-        w.trem_serial = flag("OW_TREM_SERIAL", 0) == 1;
-        w.trem_cache = flag("OW_TREM_CACHE", 1) != 0;
-        w.trem_traj = flag("OW_TREM_TRAJ", 1) != 0;
-        w.mel_rank1 = flag("OW_MEL_RANK1", 0) == 1; w.mel_lds = flag("OW_MEL_LDS", 0) == 1; w.mel_generic = flag("OW_MEL_GENERIC", 0) == 1;
-        w.mel_eng = flag("OW_MEL_ENG", 0) == 1;
-        w.eout_attn = flag("OW_EOUT_ATTN", -1); if (w.eout_attn > 1 || w.eout_attn < -1) w.eout_attn = -1;
-        w.voice_skew = flag("OW_VOICE_SKEW", 1) != 0;
-        w.pa_sort = flag("OW_PA_SORT", 1); if (w.pa_sort < 0 || w.pa_sort > 2) w.pa_sort = 1;
-        if (const char* e = std::getenv("OW_PIPE")) { const int v = std::atoi(e); w.pipe = (v >= 1 && v <= 8) ? v : 0; }
-        w.pipe_overlap = flag("OW_PIPE_OVERLAP", 0) == 1;
-        w.voice_attack = flag("OW_VOICE_ATTACK", 1) != 0;
-        w.voice_steal = flag("OW_VOICE_STEAL", 1) != 0;
-        w.voice_release = flag("OW_VOICE_RELEASE", 1) != 0;
-        w.midi_apply_early = flag("OW_MIDI_APPLY_EARLY", 1) != 0;
-        w.midi_device = flag("OW_MIDI_DEVICE", -1); if (w.midi_device > 1 || w.midi_device < -1) w.midi_device = -1;
-        w.chain_row = flag("OW_CHAIN_ROW", -1); if (w.chain_row > 1 || w.chain_row < -1) w.chain_row = -1;
-        w.chain_stream = flag("OW_CHAIN_STREAM", -1); if (w.chain_stream > 1 || w.chain_stream < -1) w.chain_stream = -1;
-        w.post_pair = flag("OW_POST_PAIR", -1); if (w.post_pair > 1 || w.post_pair < -1) w.post_pair = -1;
-        w.preamp_pair = flag("OW_PREAMP_PAIR", -1); if (w.preamp_pair > 1 || w.preamp_pair < -1) w.preamp_pair = -1;
-        w.out_direct = flag("OW_OUT_DIRECT", -1); if (w.out_direct > 1 || w.out_direct < -1) w.out_direct = -1;
-        w.host_profile = std::getenv("OW_HOST_PROFILE") != nullptr;
-        if (const char* e = std::getenv("OW_MIDI_THREADS")) { const long v = std::atol(e); if (v >= 1 && v <= 64) w.midi_threads = (int)v; }
-        if (const char* e = std::getenv("OW_CALIB_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.calib_chunk = v; }
-        if (const char* e = std::getenv("OW_PBENCH_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.pbench_chunk = v; }
-        if (const char* e = std::getenv("OW_POLY_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.poly_chunk = v; }
-        if (const char* e = std::getenv("OW_CENTROID_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.centroid_chunk = v; }
-        if (const char* e = std::getenv("OW_NOTE_AUDIT_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.note_audit_chunk = v; }
-        if (const char* e = std::getenv("OW_PUMP_CHUNK")) { const long long v = std::atoll(e); if (v >= 1) w.pump_chunk = v; }
-        w.pbench_row = flag("OW_PBENCH_ROW", -1); if (w.pbench_row > 1 || w.pbench_row < -1) w.pbench_row = -1;
+        long long v;
+#define X(type, name, dflt, env, kind, lo, hi, settable) if (switch_from_env(env, kind, lo, hi, &v)) w.name = (type)v;
+        OW_SWITCH_TABLE(X)
+#undef X
         return w;
+    }
+    bool set(const char* n, int value) {       // false: unknown name, not settable, or a value the switch refuses
+        long long v = value;
+#define X(type, name, dflt, env, kind, lo, hi, settable) if (!std::strcmp(n, #name)) { if (!(settable) || !switch_from_set(kind, lo, hi, &v)) return false; name = (type)v; return true; }
+        OW_SWITCH_TABLE(X)
+#undef X
+        return false;
+    }
+    bool get(const char* n, int* value) const {
+#define X(type, name, dflt, env, kind, lo, hi, settable) if (!std::strcmp(n, #name)) { *value = (int)std::min<long long>((long long)name, 0x7FFFFFFF); return true; }
+        OW_SWITCH_TABLE(X)
+#undef X
+        return false;
     }
 };
 

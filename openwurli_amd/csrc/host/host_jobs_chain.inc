@@ -4,41 +4,29 @@ enum { INIT_NEW = 1, INIT_RATE = 2, INIT_RESET = 0 };
 
 // Job paths (batch render, render-midi): a quad of lanes per preamp state (ow_chain_wide.h) while the jobs are too few to fill the
 // chip with one lane pair each -- their run time is then the chain's serial latency.  OW_CHAIN_WIDE=0/1 forces the choice (the
-// parity test compares the two kernels bit for bit).
-static inline bool chain_wide(size_t n_jobs) {
-    if (const char* env = std::getenv("OW_CHAIN_WIDE")) return env[0] == '1';
-    return n_jobs <= 8192;
-}
+// parity test compares the two kernels bit for bit).  These switches are read with the rest of the call's Switches, once per call.
+static inline bool chain_wide(const Switches& sw, size_t n_jobs) { return sw.chain_wide >= 0 ? sw.chain_wide == 1 : n_jobs <= 8192; }
 // OW_JOB_FUSED=0: the quad job chain as one wavefront (k_job_chain_wide) instead of preamp | output stage on two (k_job_chain_fused)
 // (two wavefronts of 400+ registers per eight jobs: 512 workgroups fill the chip, more of them take a second round -- 8 192 jobs measured
 // 319 against 191 ms -- so the fused form is for up to 4 096 jobs)
-static inline bool job_chain_fused(size_t n_jobs) {
-    if (const char* env = std::getenv("OW_JOB_FUSED")) return env[0] != '0';
-    return n_jobs <= 4096;
-}
+static inline bool job_chain_fused(const Switches& sw, size_t n_jobs) { return chain_wide(sw, n_jobs) && (sw.job_fused >= 0 ? sw.job_fused == 1 : n_jobs <= 4096); }
 // The batch render may run the voices of its jobs BESIDE this chain (ow_batch_render: k_job_voice on a second stream publishes its
 // progress, k_job_chain_fused waits chunk by chunk): only while the chain's workgroups leave SIMDs free for the voice kernel -- 2 048 jobs
-// are 256 workgroups of two one-per-SIMD wavefronts, half the chip -- so that the producer can always be scheduled.
-static inline bool job_voice_overlap(size_t n_jobs) {
-    if (const char* env = std::getenv("OW_JOB_OVERLAP")) { if (env[0] == '0') return false; }
-    return chain_wide(n_jobs) && job_chain_fused(n_jobs) && n_jobs <= 2048;
-}
+// are 256 workgroups of two one-per-SIMD wavefronts, half the chip -- so that the producer can always be scheduled.  OW_JOB_OVERLAP=0: never.
+static inline bool job_voice_overlap(const Switches& sw, size_t n_jobs) { return sw.job_overlap && job_chain_fused(sw, n_jobs) && n_jobs <= 2048; }
 // OW_JOB_ROW=0: the fused job chain with a quad per solver state (k_job_chain_fused) instead of a row of sixteen lanes (k_job_chain_row:
 // five wavefronts per eight jobs -- while they all find a SIMD of their own beside the voice kernel)
-static inline bool job_chain_row(size_t n_jobs) {
-    if (const char* env = std::getenv("OW_JOB_ROW")) return env[0] != '0';
-    return n_jobs <= 1024;
-}
-static void launch_job_chain_legacy(const OwConsts* dK, const owdev::OwJobDev* d_jobs, const double* d_in, double* d_out, size_t n_jobs, long long n,
-                                    long long stride, hipStream_t st, const int* voice_prog = nullptr) {
-    if (voice_prog && !(chain_wide(n_jobs) && job_chain_fused(n_jobs))) throw std::runtime_error("job chain: overlap with the voices needs the fused chain");
-    if (chain_wide(n_jobs) && job_chain_fused(n_jobs) && job_chain_row(n_jobs))
-        owdev::k_job_chain_row<<<dim3((unsigned)((n_jobs + 7) / 8)), dim3(320), 0, st>>>(dK, d_jobs, d_in, d_out, (int)n_jobs, n, stride, voice_prog,
-                                                                                         voice_prog ? const_cast<int*>(voice_prog) + (n_jobs + 63) / 64 : nullptr);
-    else if (chain_wide(n_jobs) && job_chain_fused(n_jobs))
-        owdev::k_job_chain_fused<<<dim3((unsigned)((n_jobs + 7) / 8)), dim3(128), 0, st>>>(dK, d_jobs, d_in, d_out, (int)n_jobs, n, stride, voice_prog,
-                                                                                           voice_prog ? const_cast<int*>(voice_prog) + (n_jobs + 63) / 64 : nullptr);
-    else if (chain_wide(n_jobs))
+static inline bool job_chain_row(const Switches& sw, size_t n_jobs) { return sw.job_row >= 0 ? sw.job_row == 1 : n_jobs <= 1024; }
+static void launch_job_chain_legacy(const Switches& sw, const OwConsts* dK, const owdev::OwJobDev* d_jobs, const double* d_in, double* d_out, size_t n_jobs,
+                                    long long n, long long stride, hipStream_t st, const int* voice_prog = nullptr) {
+    const bool wide = chain_wide(sw, n_jobs), fused = job_chain_fused(sw, n_jobs);
+    if (voice_prog && !fused) throw std::runtime_error("job chain: overlap with the voices needs the fused chain");
+    int* const gave_up = voice_prog ? const_cast<int*>(voice_prog) + (n_jobs + 63) / 64 : nullptr;
+    if (fused && job_chain_row(sw, n_jobs))
+        owdev::k_job_chain_row<<<dim3((unsigned)((n_jobs + 7) / 8)), dim3(320), 0, st>>>(dK, d_jobs, d_in, d_out, (int)n_jobs, n, stride, voice_prog, gave_up);
+    else if (fused)
+        owdev::k_job_chain_fused<<<dim3((unsigned)((n_jobs + 7) / 8)), dim3(128), 0, st>>>(dK, d_jobs, d_in, d_out, (int)n_jobs, n, stride, voice_prog, gave_up);
+    else if (wide)
         owdev::k_job_chain_wide<<<dim3((unsigned)((n_jobs + 7) / 8)), dim3(64), 0, st>>>(dK, d_jobs, d_in, d_out, (int)n_jobs, n, stride);
     else
         owdev::k_job_chain<false><<<dim3((unsigned)((n_jobs + 31) / 32)), dim3(64), 0, st>>>(dK, d_jobs, d_in, d_out, nullptr, (int)n_jobs, n, stride);
@@ -120,7 +108,7 @@ void run_job_chain(OfflineCall& call, const JobChainCfg& cfg, const std::vector<
         owdev::k_job_chain<true><<<dim3((unsigned)((n_jobs + 31) / 32)), dim3(64), 0, st>>>(dK, d_jobs, d_in, chain_out, call.mel_settled(), (int)n_jobs, n, stride,
                                                                                             trem, out_mode);
     } else if (!any_trem && !any_special && !mpa) {
-        launch_job_chain_legacy(dK, d_jobs, d_in, chain_out, n_jobs, n, stride, st, voice_prog);
+        launch_job_chain_legacy(call.sw, dK, d_jobs, d_in, chain_out, n_jobs, n, stride, st, voice_prog);
     } else {
         owdev::k_job_chain<false><<<dim3((unsigned)((n_jobs + 31) / 32)), dim3(64), 0, st>>>(dK, d_jobs, d_in, chain_out, nullptr, (int)n_jobs, n, stride, trem, out_mode);
     }
@@ -134,35 +122,4 @@ void run_job_chain(OfflineCall& call, const JobChainCfg& cfg, const std::vector<
     }
     HIP_OK(hipStreamSynchronize(st));
 }
-
-// chain (re)initialisation of engines [e0, e0+ne): DC states on the device, then the Twin-T settle
-// (50 warm-up steps at the codegen matrices + 2 s at the pool rate), all in the product kernels.
-// Pools this small leave SIMDs idle, and the oscillator's serial latency is their block time: four lanes per engine (ow_trem_wide.h).
-// Melange power amp: engines dispatched by falling demand (OW_PA_SORT=0: in index order -- the same samples, tested)
-static bool power_amp_ordered(const ow_pool* p) { return p->sw.pa_sort != 0; }
-// engines of k_post_mpa the chip holds at once: two workgroups of PA_EPB per CU (LDS)
-static int power_amp_resident_engines(const ow_pool* p) {
-    if (p->sw.pa_sort == 2) return PA_EPB;      // '2': order every block of more than one workgroup (tests)
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || cus <= 0) cus = 256;
-    return cus * 2 * PA_EPB;
-}
-// OW_TREM_WIDE=0/1 forces the choice (the parity test compares the two kernels bit for bit).
-static inline bool trem_wide(const ow_pool* p, int ne) { return p->sw.trem_wide >= 0 ? p->sw.trem_wide == 1 : ne <= 16384; }
-// lane = group tremolo kernel at pool scale, measured at 131 072 engines / oscillators: serialised in front of the voices 31.8 ms per
-// block (voices 12.8, tremolo 9.1 on an empty chip), overlapped 29.7 ms -- each kernel alone leaves issue slots the other can use.  So
-// the default stays overlapped; the serialised schedule is how the two kernels' own times are measured (profiles/).
-static inline bool trem_serialised(const ow_pool* p) { return p->sw.trem_serial; }
-// legacy preamp with a quad per solver state (k_preamp_wide): while the pool leaves most SIMDs empty the kernel's time is the serial
-// latency of one sample, which the quad shortens; beyond ~4 096 engines the lane-pair kernel's lower instruction count wins
-static inline bool preamp_wide(const ow_pool* p, int ne) { return p->sw.preamp_wide >= 0 ? p->sw.preamp_wide == 1 : ne <= 4096; }
-// ... and the output stage in the same launch behind it (k_chain_fused): legacy preamp + behavioural power amp only
-static inline bool chain_fused(const ow_pool* p, int ne) {
-    if (p->hc.preamp_kind != OW_PREAMP_LEGACY8 || p->power_amp_kind != OW_POWER_AMP_BEHAVIORAL) return false;
-    // (measured by pool size, tools/probe_row_crossover.py, ms per 512-sample block: 2 048 engines fused 1.99 / two launches 2.37; 4 096 engines
-    // 2.97 / 2.59 -- 512 two-wavefront workgroups are the last that find their SIMDs free)
-    return p->sw.chain_fused >= 0 ? p->sw.chain_fused == 1 : (preamp_wide(p, ne) && ne <= 2048);
-}
-// ... with the row step (k_chain_row): while every preamp wavefront (two engines) has a SIMD of its own
-static inline bool chain_row(const ow_pool* p, int ne) { return p->sw.chain_row >= 0 ? p->sw.chain_row == 1 : ne <= 1024; }
 }  // namespace

@@ -1,4 +1,4 @@
-// openwurli-hip host side, part of openwurli_hip.hip (one translation unit): tremolo phase groups, chain (re)initialisation, voice lists, render_range, post-render bookkeeping, pool life cycle.
+// openwurli-hip host side, part of openwurli_hip.hip (one translation unit): tremolo phase groups, chain (re)initialisation, kernel choice of a block, voice lists, render_range and its phases, post-render bookkeeping, pool life cycle.
 namespace {
 // ---- tremolo phase groups (see ow_pool) ---------------------------------------------------------------------------------
 void trem_groups_changed(ow_pool* p) {
@@ -240,28 +240,78 @@ void vm_settle_applied(ow_pool* p) {
     if (p->d_prev_tr) p->attn_resync = true;      // p->transient moved without the device's copy
 }
 
-// Melange preamp: the default kernel re-factors the 12x12 system for every sample whose R_ldr moved, operation for operation like the
-// reference (ow_melange_col.h).  OW_MEL_RANK1=1 selects the rank-one (Sherman-Morrison) kernel instead: mathematically the same, but
-// without the LU's rounding noise, i.e. up to 1.8e-7 V away from the reference while R_ldr moves fast (DESIGN.md deviation 6);
-// OW_MEL_LDS=1 the round-2 literal kernel (S of every engine in LDS); OW_MEL_GENERIC=1 the literal kernels without their fast path.
-static inline bool eout_attention(const ow_pool* p, int ne) { return p->d_attn && (p->sw.eout_attn < 0 ? ne >= 8192 : p->sw.eout_attn != 0); }
-static inline bool melange_rank_one(const ow_pool* p) { return p->sw.mel_rank1; }
-static inline bool melange_lds_matrix(const ow_pool* p) { return p->sw.mel_lds; }
-static inline bool melange_generic_only(const ow_pool* p) { return p->sw.mel_generic; }
-// OW_MEL_ENG=1: lane = engine (ow_melange_eng.h: the rebuild once per engine instead of once per solver state, 64 engines per wavefront).
-// Bit-identical; measured 39.2 against 40.4 ms per 131 072-engine block and 45 against 21 ms at 65 536 (one wavefront per SIMD): not the default.
-static inline bool melange_lane_engine(const ow_pool* p, int) { return p->sw.mel_eng != 0; }
+// ---- which kernels a block gets ------------------------------------------------------------------------------------------------
+// Pure functions of the latched switches, the pool's build and the block's size: no pool, no device (ow_test_block_plan and
+// tests/test_block_plan_host.py pin the table).  A tri-state switch forces its choice with 0 / 1 and leaves it to the size rule at -1.
+static inline bool forced_or(int sw, bool by_size) { return sw >= 0 ? sw == 1 : by_size; }
+// OW_TREM_WIDE: pools this small leave SIMDs idle, and the oscillator's serial latency is their block time: four lanes per oscillator
+// (ow_trem_wide.h).  (OW_TREM_SERIAL, measured with lane = group at 131 072 oscillators: serialised in front of the voices 31.8 ms per
+// block -- voices 12.8, tremolo 9.1 on an empty chip --, overlapped 29.7 ms; the serialised schedule is how the two kernels' own times
+// are measured, profiles/.)
+static inline bool trem_wide(const Switches& sw, int n_lead) { return forced_or(sw.trem_wide, n_lead <= 16384); }
+// OW_PREAMP_WIDE: legacy preamp with a quad per solver state (k_preamp_wide): while the pool leaves most SIMDs empty the kernel's time is
+// the serial latency of one sample, which the quad shortens; beyond ~4 096 engines the lane-pair kernel's lower instruction count wins
+static inline bool preamp_wide(const Switches& sw, int ne) { return forced_or(sw.preamp_wide, ne <= 4096); }
+static inline bool eout_attention(const ow_pool* p, int ne) { return p->d_attn && forced_or(p->sw.eout_attn, ne >= 8192); }
 
-// Stages of the staged render.  Off by default: OW_PIPE=n (2..8) cuts big ranges (>= 32 768 engines) into n engine stages on their own
-// streams, chained stage to stage, so that the output copy of a stage runs beside the kernels of the next one.  Measured: stages cost
-// more than the copy overlap they buy (DESIGN.md, "what did not work").
-static inline int pipeline_stages(const ow_pool* p, int ne) {
-    if (ne < 32768) return 1;
-    return p->sw.pipe ? p->sw.pipe : 1;
+// What launch_chain runs between the voice sums and the preamp rows (PREAMP_*) or the finished rows (CHAIN_*: output stage included).
+enum ChainKernel { CHAIN_NONE, CHAIN_ROW_OS_8, CHAIN_ROW_OS_16, CHAIN_ROW_8, CHAIN_ROW_16, CHAIN_FUSED_OS, CHAIN_FUSED, CHAIN_STREAM,
+                   PREAMP_MEL_ENG, PREAMP_MEL_COL, PREAMP_MEL_LIT, PREAMP_MEL, PREAMP_WIDE, PREAMP_PAIR, PREAMP_LANE };
+enum PostKernel { POST_NONE, POST_MPA, POST_PAIR, POST_OS, POST_BASE };
+static const char* const CHAIN_KERNEL_NAME[] = {"", "k_chain_row<true,8>", "k_chain_row<true,16>", "k_chain_row<false,8>", "k_chain_row<false,16>",
+                                                "k_chain_fused<true>", "k_chain_fused<false>", "k_chain_stream", "k_preamp_mel_eng", "k_preamp_mel_col",
+                                                "k_preamp_mel_lit", "k_preamp_mel", "k_preamp_wide", "k_preamp_pair", "k_preamp"};
+static const char* const POST_KERNEL_NAME[] = {"", "k_post_mpa", "k_post<false,true>", "k_post<true>", "k_post<false>"};
+static inline bool chain_has_output_stage(ChainKernel k) { return k >= CHAIN_ROW_OS_8 && k <= CHAIN_STREAM; }
+
+ChainKernel choose_chain(const Switches& sw, int preamp_kind, int power_amp_kind, bool oversample, bool ml_sparse_ok, int ne, int L, bool to_pinned_block) {
+    if (ne <= 0) return CHAIN_NONE;
+    const bool legacy = preamp_kind == OW_PREAMP_LEGACY8 && power_amp_kind == OW_POWER_AMP_BEHAVIORAL;
+    const bool wide = preamp_wide(sw, ne);
+    // OW_CHAIN_FUSED: the output stage in the same launch behind the quad preamp (k_chain_fused, ow_chain_wide.h): legacy preamp + behavioural
+    // power amp only.  (Measured by pool size, tools/probe_row_crossover.py, ms per 512-sample block: 2 048 engines fused 1.99 / two launches
+    // 2.37; 4 096 engines 2.97 / 2.59 -- 512 two-wavefront workgroups are the last that find their SIMDs free.)
+    if (legacy && forced_or(sw.chain_fused, wide && ne <= 2048)) {
+        // OW_CHAIN_ROW: ... with one solver state per row of sixteen lanes (ow_chain_row.h: four preamp wavefronts + the output-stage one per
+        // eight engines) while every preamp wavefront has a SIMD of its own; blocks of up to 128 samples keep eight rows in flight
+        if (!forced_or(sw.chain_row, ne <= 1024)) return oversample ? CHAIN_FUSED_OS : CHAIN_FUSED;
+        if (oversample) return L <= 128 ? CHAIN_ROW_OS_8 : CHAIN_ROW_OS_16;
+        return L <= 128 ? CHAIN_ROW_8 : CHAIN_ROW_16;
+    }
+    // k_chain_stream (ow_chain_stream.h): legacy preamp + behavioural amp, oversampled chain, pools too big for the quad kernels: preamp and
+    // output stage alternate per 64-sample chunk in one launch.  Default: when the block goes to a pinned host block (the point of it: no
+    // copy trails the launch); OW_CHAIN_STREAM=1 always.
+    if (legacy && oversample && !wide && forced_or(sw.chain_stream, to_pinned_block)) return CHAIN_STREAM;
+    if (preamp_kind == OW_PREAMP_MELANGE12) {
+        // The default kernel re-factors the 12x12 system for every sample whose R_ldr moved, operation for operation like the reference
+        // (ow_melange_col.h).  OW_MEL_RANK1=1 selects the rank-one (Sherman-Morrison) kernel instead: mathematically the same, but without the
+        // LU's rounding noise, i.e. up to 1.8e-7 V away from the reference while R_ldr moves fast (DESIGN.md deviation 6); OW_MEL_LDS=1 the
+        // round-2 literal kernel (S of every engine in LDS; also what a chain rate without the compiled-in sparsity pattern gets);
+        // OW_MEL_GENERIC=1 the literal kernels without their fast path.  OW_MEL_ENG=1: lane = engine (ow_melange_eng.h: the rebuild once per
+        // engine instead of once per solver state).  Bit-identical; measured 39.2 against 40.4 ms per 131 072-engine block and 45 against
+        // 21 ms at 65 536 (one wavefront per SIMD): not the default.
+        if (sw.mel_rank1) return PREAMP_MEL;
+        if (!ml_sparse_ok || sw.mel_lds) return PREAMP_MEL_LIT;
+        return sw.mel_eng ? PREAMP_MEL_ENG : PREAMP_MEL_COL;
+    }
+    if (wide) return PREAMP_WIDE;
+    // OW_PREAMP_PAIR: lane = engine, main and shadow state in one lane: half the wavefronts, two per SIMD from 131 072 engines
+    return forced_or(sw.preamp_pair, ne >= 131072) ? PREAMP_PAIR : PREAMP_LANE;
 }
-// OW_PIPE_OVERLAP=1: chain the stages voice kernel to voice kernel instead of stage to stage, so that the chain kernels of stage k run
-// beside the voice kernel of stage k+1.  Measured slower at every stage count; kept as a switch so the measurement can be repeated.
-static inline bool pipeline_overlap(const ow_pool* p) { return p->sw.pipe_overlap; }
+PostKernel choose_post(const Switches& sw, int power_amp_kind, bool oversample, int ne, ChainKernel chain) {
+    if (ne <= 0 || chain == CHAIN_NONE || chain_has_output_stage(chain)) return POST_NONE;
+    if (power_amp_kind == OW_POWER_AMP_MELANGE) return POST_MPA;
+    if (!oversample) return POST_BASE;
+    return forced_or(sw.post_pair, ne >= 131072) ? POST_PAIR : POST_OS;       // OW_POST_PAIR: lane = engine (two wavefronts per SIMD without it)
+}
+// Melange power amp: engines dispatched by falling demand (OW_PA_SORT=0: in index order -- the same samples, tested) when the block has more
+// engines than k_post_mpa holds on the chip at once: two workgroups of PA_EPB per CU (LDS).  Reads a device attribute: not part of the choice above.
+static int power_amp_resident_engines(const ow_pool* p) {
+    if (p->sw.pa_sort == 2) return PA_EPB;      // '2': order every block of more than one workgroup (tests)
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || cus <= 0) cus = 256;
+    return cus * 2 * PA_EPB;
+}
 
 // Deal the sounding voices of engines [e0, e0+ne) into wavefront-sized blocks (see ow_kernels.h, "Packed dispatch").
 // general = engines whose status after the previous block reported a transient phase, or that receive ops in this block (a note-on
@@ -270,17 +320,12 @@ void build_voice_lists(ow_pool* p, int e0, int ne) {
     // Big ranges are cut into T engine slices that are packed independently (each slice starts on a block boundary, so at most
     // T - 1 blocks are less full than they could be): pass 1 sizes the three lists of every slice, a prefix sum places them,
     // pass 2 writes the entries.
-    const int NP = pipeline_stages(p, ne);                     // stage boundaries exist whether or not this block uses them
-    size_t T = ne >= 16384 ? std::min<size_t>(effective_cpus(), 32) : 1;
-    if (NP > 1) T = std::max<size_t>(NP, T - T % (size_t)NP);   // stages are whole numbers of slices
-    // slices (and with them the stages of a staged render) start on multiples of 32 engines: the chain kernels' workgroups then never
-    // straddle a stage boundary, and per-workgroup scratch indexed by (first engine / 32 + block) is disjoint between stages
+    const size_t T = ne >= 16384 ? std::min<size_t>(effective_cpus(), 32) : 1;
+    // slices start on multiples of 32 engines, like the chain kernels' workgroups
     const int per = (int)(((ne + T - 1) / T + 31) / 32 * 32);
-    using Fill = ow_pool::SliceStart;
-    Fill size[OW_MAX_SLICES];
-    Fill* start = p->slice_start;                              // T <= 32; kept: stage k launches the blocks of its slices
-    start[0] = Fill();
-    p->slice_T = (int)T; p->slice_per = per;
+    // entry offsets of a slice in the four lists; h: pass-1 hashes of the slice
+    struct Fill { uint32_t s = 0, g = 0, t = 0, a = 0; uint64_t h[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}}; };
+    Fill size[OW_MAX_SLICES], start[OW_MAX_SLICES + 1];        // T <= 32
     auto pack = [&](size_t t, uint32_t* S, uint32_t* G, uint32_t* Tl, uint32_t* A, Fill& f) {   // a null list: count (and hash) only
         auto pad = [](uint32_t* a, uint32_t& n) { while (n & 63u) { if (a) a[n] = 0xFFFFFFFFu; ++n; } };
         auto put_l = [&](int list, uint32_t* a, uint32_t& n, uint32_t e, uint64_t mask, bool own_block) {
@@ -358,69 +403,77 @@ void build_voice_lists(ow_pool* p, int e0, int ne) {
 static void launch_tremolo(ow_pool* p, hipStream_t tt, double* rbuf, int n_os) {
     const int I = (int)p->I, nl = p->n_lead;
     if (p->tremolo_kind == OW_TREMOLO_LEGACY_LFO) owdev::k_tremolo_lfo<<<dim3((nl + 63) / 64), dim3(64), 0, tt>>>(p->dK, p->d_cs, rbuf, I, (long long)n_os, p->d_leaders, nl, 0LL);
-    else if (trem_wide(p, nl)) owdev::k_tremolo_wide<false><<<dim3((nl + 15) / 16), dim3(64), 0, tt>>>(p->dK, p->d_cs, rbuf, I, (long long)n_os, p->d_leaders, nl);
+    else if (trem_wide(p->sw, nl)) owdev::k_tremolo_wide<false><<<dim3((nl + 15) / 16), dim3(64), 0, tt>>>(p->dK, p->d_cs, rbuf, I, (long long)n_os, p->d_leaders, nl);
     else owdev::k_tremolo<<<dim3((nl + 63) / 64), dim3(64), 0, tt>>>(p->dK, p->d_cs, rbuf, I, n_os, p->d_leaders, nl);
 }
 
-// One render of `len` samples for engines [e0, e0+ne).  with_voices=false skips the voice kernels
-// (warm-up of engines whose voices were just freed).
-// out_host != nullptr: rows [e0, e0+ne) of the block are copied to out_host[(e - e0) * out_stride] as their stages finish.
-void render_range(ow_pool* p, int e0, int ne, size_t len, bool with_voices, float* out_host = nullptr, size_t out_stride = 0) {
-    if (len > p->Lcap) { HIP_OK(hipStreamSynchronize(p->stream)); alloc_stream_buffers(p, len); }  // auto-grow, engine.rs:430 (also after a grow that failed: Lcap 0)
-    const int I = (int)p->I;
-    const int L = (int)len, Lcap = (int)p->Lcap;
-    p->out_ld = len;
-    hipStream_t st = p->stream, tt = p->stream_trem;
-    vm_wait_download(p);                     // a burst applied on the device: the host's copy of the voice-pool states is complete from here on
-    // ---- tremolo: CdS cell resistance of this block
-    const int n_os = L * (p->hc.oversample ? 2 : 1);
-    const size_t rb_half = (size_t)2 * p->Lcap * p->I;
-    const bool chain = !p->voices_only;     // a voices-only pool (ow_render_note) stops at the voice sums
-    const bool whole = e0 == 0 && ne == I;
-    // (a) engines on the shared trajectory read r_ldr[t .. t + n_os) at their own t = clock - birth: make the store reach the oldest one's
-    //     block (nothing to do unless this pool holds the process's oldest engine), plus one block ahead on the store's own stream
-    owdev::OwTremSrc tsrc{nullptr, p->d_lead, nullptr, p->d_birth};
-    hipEvent_t traj_ready = nullptr;
-    if (chain && p->traj) {
-        long long mn = p->min_birth;
-        if (!whole) { mn = p->trem_clock; for (int k = 0; k < ne; ++k) if (p->h_birth[e0 + k] != OW_OFF_TRAJ) mn = std::min(mn, p->h_birth[e0 + k]); }
-        if ((size_t)(p->trem_clock - mn) + (size_t)n_os > p->traj->cap_max) { trem_evict(p, e0, ne, n_os); mn = p->trem_clock; for (int k = 0; k < ne; ++k) if (p->h_birth[e0 + k] != OW_OFF_TRAJ) mn = std::min(mn, p->h_birth[e0 + k]); }
-        size_t need = (size_t)(p->trem_clock - mn) + (size_t)n_os;
-        bool ask = false, must = false, feed = false;
-        {
-            std::lock_guard<std::mutex> lk(p->traj->mu);
-            must = need > p->traj->cap;                        // the helper did not get there in time (it is asked a lead + 30 s before)
-            if (!must && p->traj->wants_growth(need)) { p->traj->grow_requested = true; ask = true; }
-        }
-        if (must) {                                            // cold: allocates on this thread, like the reference's buffer auto-grow
-            try { p->traj->grow_to(std::max(need, p->traj->cap * 2)); }
-            catch (const std::exception& ex) {
-                // no memory for a longer store (a crowded device): it stays as long as it is -- as the helper thread's failure path decides --
-                // and the engines that have outgrown it continue on oscillators of their own instead of retrying the allocation every block
-                (void)hipGetLastError();
-                { std::lock_guard<std::mutex> lk(p->traj->mu); p->traj->cap_max = p->traj->cap; p->traj->grow_requested = false; }
-                std::fprintf(stderr, "openwurli-hip: tremolo trajectory store stays at %zu samples (%s)\n", p->traj->cap, ex.what());
-                trem_evict(p, e0, ne, n_os);
-                mn = p->trem_clock;
-                for (int k = 0; k < ne; ++k) if (p->h_birth[e0 + k] != OW_OFF_TRAJ) mn = std::min(mn, p->h_birth[e0 + k]);
-                need = (size_t)(p->trem_clock - mn) + (size_t)n_os;
-            }
-        }
-        if (ask) traj_grower().ask(p->traj);
-        {
-            std::lock_guard<std::mutex> lk(p->traj->mu);
-            traj_ready = p->traj->cover(need, (size_t)n_os, p->I < 4096 ? p->traj->lead : 0, &feed);
-            tsrc.traj = p->traj->d_r + p->trem_clock;         // (under the lock: a growth swaps the buffer)
-        }
-        if (feed) traj_grower().feed(p->traj);
+// ---- one block: the phases of render_range, in the order of DESIGN.md 4.1 ----------------------------------------------------------
+struct Block {
+    int e0 = 0, ne = 0, L = 0, n_os = 0;     // engines [e0, e0+ne), samples at the host rate / at the chain rate
+    size_t len = 0;
+    bool whole = false;                      // the whole pool
+    bool chain = false;                      // false: a voices-only pool (ow_render_note) stops at the voice sums
+    float* out_host = nullptr;               // rows go to out_host[(e - e0) * out_stride] ...
+    size_t out_stride = 0;
+    float* out_direct = nullptr;             // ... written by the output stage itself: the target's device address when it lies in a pinned block of ow_host_alloc
+    owdev::OwTremSrc tsrc{nullptr, nullptr, nullptr, nullptr};   // where the chain kernels read this block's R_ldr
+};
+
+// min over the range's engines on the trajectory of birth[e]
+static long long range_min_birth(const ow_pool* p, int e0, int ne) {
+    long long mn = p->trem_clock;
+    for (int k = 0; k < ne; ++k) if (p->h_birth[e0 + k] != OW_OFF_TRAJ) mn = std::min(mn, p->h_birth[e0 + k]);
+    return mn;
+}
+// Engines on the shared trajectory read r_ldr[t .. t + n_os) at their own t = clock - birth: make the store reach the oldest one's block
+// (nothing to do unless this pool holds the process's oldest engine), plus one block ahead on the store's own stream.  Returns the event
+// the chain has to wait for (nullptr: the samples are there).
+static hipEvent_t traj_cover_block(ow_pool* p, Block& b) {
+    const int e0 = b.e0, ne = b.ne, n_os = b.n_os;
+    long long mn = b.whole ? p->min_birth : range_min_birth(p, e0, ne);
+    if ((size_t)(p->trem_clock - mn) + (size_t)n_os > p->traj->cap_max) { trem_evict(p, e0, ne, n_os); mn = range_min_birth(p, e0, ne); }
+    size_t need = (size_t)(p->trem_clock - mn) + (size_t)n_os;
+    bool ask = false, must = false, feed = false;
+    {
+        std::lock_guard<std::mutex> lk(p->traj->mu);
+        must = need > p->traj->cap;                        // the helper did not get there in time (it is asked a lead + 30 s before)
+        if (!must && p->traj->wants_growth(need)) { p->traj->grow_requested = true; ask = true; }
     }
-    // (b) engines with an oscillator of their own (phase groups): already there if the block-ahead speculation hit
-    const bool hit = chain && p->spec.valid && p->spec.e0 == e0 && p->spec.ne == ne && p->spec.n_os == n_os;
+    if (must) {                                            // cold: allocates on this thread, like the reference's buffer auto-grow
+        try { p->traj->grow_to(std::max(need, p->traj->cap * 2)); }
+        catch (const std::exception& ex) {
+            // no memory for a longer store (a crowded device): it stays as long as it is -- as the helper thread's failure path decides --
+            // and the engines that have outgrown it continue on oscillators of their own instead of retrying the allocation every block
+            (void)hipGetLastError();
+            { std::lock_guard<std::mutex> lk(p->traj->mu); p->traj->cap_max = p->traj->cap; p->traj->grow_requested = false; }
+            std::fprintf(stderr, "openwurli-hip: tremolo trajectory store stays at %zu samples (%s)\n", p->traj->cap, ex.what());
+            trem_evict(p, e0, ne, n_os);
+            need = (size_t)(p->trem_clock - range_min_birth(p, e0, ne)) + (size_t)n_os;
+        }
+    }
+    if (ask) traj_grower().ask(p->traj);
+    hipEvent_t ready;
+    {
+        std::lock_guard<std::mutex> lk(p->traj->mu);
+        ready = p->traj->cover(need, (size_t)n_os, p->I < 4096 ? p->traj->lead : 0, &feed);
+        b.tsrc.traj = p->traj->d_r + p->trem_clock;        // (under the lock: a growth swaps the buffer)
+    }
+    if (feed) traj_grower().feed(p->traj);
+    return ready;
+}
+
+// Engines with an oscillator of their own (phase groups): this block's R_ldr is already there if the block-ahead speculation hit; then
+// the next block's, speculatively.  Returns the half of rbuf (index of ev_trem) the chain has to wait for, -1: no oscillator ran.
+static int trem_block(ow_pool* p, Block& b) {
+    const int e0 = b.e0, ne = b.ne, n_os = b.n_os;
+    hipStream_t tt = p->stream_trem;
+    const size_t rb_half = (size_t)2 * p->Lcap * p->I;
+    const bool hit = b.chain && p->spec.valid && p->spec.e0 == e0 && p->spec.ne == ne && p->spec.n_os == n_os;
     if (p->spec.valid && !hit) {   // mis-speculated (different block length / engine range): roll the oscillator back
         HIP_OK(hipMemcpyAsync(p->d_cs, p->d_trem_backup, sizeof(double) * 18 * p->I, hipMemcpyDeviceToDevice, tt));
         p->spec.valid = false;
     }
-    if (chain) {
+    if (b.chain) {
         // a sub-range advances on its own: its engines leave the phase groups they share with engines outside it (no-op for the whole pool
         // and for a range that was just initialised); then the oscillators to run are the group leaders inside the range
         if (p->n_on_traj < p->I) trem_split_at_range(p, e0, ne);
@@ -432,12 +485,12 @@ void render_range(ow_pool* p, int e0, int ne, size_t len, bool with_voices, floa
             HIP_OK(hipEventRecord(p->ev_trem[p->rb_cur], tt));
         }
     }
-    const bool own_osc = chain && p->n_lead > 0;
-    const double* rb_now = p->d_rbuf + p->rb_cur * rb_half;
-    tsrc.rbuf = rb_now;
-    const int rb_now_idx = p->rb_cur;
-    // ---- next block, speculatively: back up the oscillator rows, then run ahead into the other half
-    auto launch_block_ahead = [&] {
+    const bool own_osc = b.chain && p->n_lead > 0;
+    b.tsrc.rbuf = p->d_rbuf + p->rb_cur * rb_half;
+    // The oscillators of the NEXT block go first: they need nothing from the host, so they run while the host packs ops and voice lists,
+    // and their wavefronts (one per SIMD at 65 536 of them) are resident before the voice kernel fills the rest.  (k_apply_ops is
+    // register-capped so that it fits beside them.)  Back up the oscillator rows, then run ahead into the other half.
+    if (own_osc) {
         const int nxt = p->rb_cur ^ 1;
         HIP_OK(hipMemcpyAsync(p->d_trem_backup, p->d_cs, sizeof(double) * 18 * p->I, hipMemcpyDeviceToDevice, tt));
         if (p->profiling) HIP_OK(hipEventRecord(p->ev[6], tt));
@@ -445,21 +498,23 @@ void render_range(ow_pool* p, int e0, int ne, size_t len, bool with_voices, floa
         if (p->profiling) HIP_OK(hipEventRecord(p->ev[7], tt));
         HIP_OK(hipEventRecord(p->ev_trem[nxt], tt));
         p->spec.valid = true; p->spec.e0 = e0; p->spec.ne = ne; p->spec.n_os = n_os;
-    };
-    // The oscillators go first: they need nothing from the host, so they run while the host packs ops and voice lists, and their
-    // wavefronts (one per SIMD at 65 536 of them) are resident before the voice kernel fills the rest.  (k_apply_ops is register-capped
-    // so that it fits beside them.)
-    if (own_osc) launch_block_ahead();
-    else if (chain && p->profiling) { HIP_OK(hipEventRecord(p->ev[6], tt)); HIP_OK(hipEventRecord(p->ev[7], tt)); }
-    // OW_TREM_SERIAL=1 (measurement switch, see trem_serialised): the voices of this block wait for the block-ahead oscillators
-    if (own_osc && trem_serialised(p)) HIP_OK(hipStreamWaitEvent(st, p->ev_trem[p->rb_cur ^ 1], 0));
-    // ---- per-engine args + ops: only engines whose host state changed are touched (the rest keep their
-    // uploaded args; a steady-state step of a large pool does no per-engine host work here)
-    // Large pools split the range over host threads: slice t counts its pending ops, a prefix sum places the slices in h_ops,
-    // then every slice packs its own engines (a 65536-engine re-strike moves ~8 M ops; one thread took ~100 ms for it).
+    } else if (b.chain && p->profiling) { HIP_OK(hipEventRecord(p->ev[6], tt)); HIP_OK(hipEventRecord(p->ev[7], tt)); }
+    // OW_TREM_SERIAL=1 (measurement switch, see trem_wide): the voices of this block wait for the block-ahead oscillators
+    if (own_osc && p->sw.trem_serial) HIP_OK(hipStreamWaitEvent(p->stream, p->ev_trem[p->rb_cur ^ 1], 0));
+    return own_osc || hit ? p->rb_cur : -1;
+}
+
+// Per-engine args + ops: only engines whose host state changed are touched (the rest keep their uploaded args; a steady-state step of
+// a large pool does no per-engine host work here).  Large pools split the range over host threads: slice t counts its pending ops, a
+// prefix sum places the slices in h_ops, then every slice packs its own engines (a 65536-engine re-strike moves ~8 M ops; one thread
+// took ~100 ms for it).
+struct Packed { bool any_dirty = false; size_t n_ops = 0; uint32_t n_act = 0; bool any_main = false, any_steal = false; };
+static Packed pack_args_and_ops(ow_pool* p, const Block& b) {
+    const int e0 = b.e0, ne = b.ne;
+    Packed r;
     // A steady block of the whole pool -- no engine touched since the last one -- skips the per-engine scans below (0.2 ms at 131 072)
-    const bool untouched = whole && !__atomic_load_n(&p->dirty_any, __ATOMIC_RELAXED) && !p->args_stale && p->any_cache_valid;
-    if (whole) __atomic_store_n(&p->dirty_any, (uint8_t)0, __ATOMIC_RELAXED);   // engines touched from here on belong to the next block
+    const bool untouched = b.whole && !__atomic_load_n(&p->dirty_any, __ATOMIC_RELAXED) && !p->args_stale && p->any_cache_valid;
+    if (b.whole) __atomic_store_n(&p->dirty_any, (uint8_t)0, __ATOMIC_RELAXED);   // engines touched from here on belong to the next block
     size_t n_dirty = 0;
     if (!untouched) for (int k = 0; k < ne; ++k) n_dirty += p->dirty[e0 + k];     // dirty[] holds 0/1
     size_t T = (n_dirty >= 4096) ? std::min<size_t>(effective_cpus(), 32) : 1;
@@ -477,11 +532,10 @@ void render_range(ow_pool* p, int e0, int ne, size_t len, bool with_voices, floa
         cnt[t + 1] = c; dirty_t[t] = d;
     };
     if (!untouched) Workers::get().each(T, count_slice);
-    bool any_dirty = false;
-    for (size_t t = 0; t < T; ++t) { any_dirty = any_dirty || dirty_t[t]; cnt[t + 1] += cnt[t]; }
-    const size_t n_ops = cnt[T];
-    ensure_ops_capacity(p, n_ops);
-    if (any_dirty || p->args_stale) {
+    for (size_t t = 0; t < T; ++t) { r.any_dirty = r.any_dirty || dirty_t[t]; cnt[t + 1] += cnt[t]; }
+    r.n_ops = cnt[T];
+    ensure_ops_capacity(p, r.n_ops);
+    if (r.any_dirty || p->args_stale) {
         auto pack_slice = [&](size_t t) {
             size_t op_pos = cnt[t];
             const int k1 = std::min(ne, (int)(t + 1) * per);
@@ -535,8 +589,7 @@ void render_range(ow_pool* p, int e0, int ne, size_t len, bool with_voices, floa
     // One parallel pass over the args of the range (13 MB at 131 072 engines: ~1 ms per walk on one thread, and the blocks after a
     // whole-pool re-strike used to take two): does any engine sound, and which engines have ops (slice t lists its own into its part of
     // h_op_engines; the parts are closed up below).
-    bool any_main = p->any_main_c, any_steal = p->any_steal_c;
-    uint32_t n_act = 0;
+    r.any_main = p->any_main_c; r.any_steal = p->any_steal_c;
     if (!untouched) {
         const size_t TA = ne >= 16384 ? std::min<size_t>(effective_cpus(), 32) : 1;
         const int per_a = (int)((ne + TA - 1) / TA);
@@ -554,179 +607,147 @@ void render_range(ow_pool* p, int e0, int ne, size_t len, bool with_voices, floa
             act_n[t] = n; any_m[t] = m; any_s[t] = sl;
         };
         Workers::get().each(TA, scan_slice);
-        any_main = false; any_steal = false;
+        r.any_main = false; r.any_steal = false;
         for (size_t t = 0; t < TA; ++t) {
-            any_main |= any_m[t] != 0; any_steal |= any_s[t] != 0;
-            if (act_n[t] && n_act != (uint32_t)(t * per_a)) std::memmove(p->h_op_engines + n_act, p->h_op_engines + t * per_a, sizeof(uint32_t) * act_n[t]);
-            n_act += act_n[t];
+            r.any_main |= any_m[t] != 0; r.any_steal |= any_s[t] != 0;
+            if (act_n[t] && r.n_act != (uint32_t)(t * per_a)) std::memmove(p->h_op_engines + r.n_act, p->h_op_engines + t * per_a, sizeof(uint32_t) * act_n[t]);
+            r.n_act += act_n[t];
         }
-        if (whole) { p->any_main_c = any_main; p->any_steal_c = any_steal; p->any_cache_valid = true; }
+        if (b.whole) { p->any_main_c = r.any_main; p->any_steal_c = r.any_steal; p->any_cache_valid = true; }
     }
+    return r;
+}
+
+static void upload_and_apply_ops(ow_pool* p, const Block& b, const Packed& pk) {
+    const int e0 = b.e0, ne = b.ne;
+    hipStream_t st = p->stream;
     // args carry one-shot fields (ops, setter targets): upload when anything changed, and once more afterwards to clear them
-    if (any_dirty || p->args_stale) {
+    if (pk.any_dirty || p->args_stale) {
         HIP_OK(hipMemcpyAsync(p->d_args + e0, p->h_args + e0, sizeof(OwEngineArgs) * ne, hipMemcpyHostToDevice, st));
-        p->args_stale = any_dirty;
+        p->args_stale = pk.any_dirty;
     }
     HIP_OK(hipMemsetAsync(p->d_eout + e0, 0, sizeof(OwEngineOut) * ne, st));
     if (p->profiling) HIP_OK(hipEventRecord(p->ev[0], st));
-    if (n_ops || p->dev_ops_pending) {
-        if (n_ops) HIP_OK(hipMemcpyAsync(p->d_ops, p->h_ops, sizeof(OwOp) * n_ops, hipMemcpyHostToDevice, st));
+    if (pk.n_ops || p->dev_ops_pending) {
+        if (pk.n_ops) HIP_OK(hipMemcpyAsync(p->d_ops, p->h_ops, sizeof(OwOp) * pk.n_ops, hipMemcpyHostToDevice, st));
         for (const ow_pool::OpTail& t : p->op_tails)
             HIP_OK(hipMemcpyAsync(p->d_ops_fix + t.dst, p->d_ops + t.src, sizeof(OwOp) * t.n, hipMemcpyDeviceToDevice, st));
         p->op_tails.clear();
-        // one block per engine that has ops (listed by the scan above; an untouched range has none)
-        if (n_act) {
-            HIP_OK(hipMemcpyAsync(p->d_op_engines, p->h_op_engines, sizeof(uint32_t) * n_act, hipMemcpyHostToDevice, st));
-            owdev::k_apply_ops<<<dim3(n_act), dim3(64), 0, st>>>(p->dK, p->d_nt, p->d_vrec, p->d_args, p->d_ops, p->d_op_engines, p->d_ops_fix);
+        // one block per engine that has ops (listed by the scan of pack_args_and_ops; an untouched range has none)
+        if (pk.n_act) {
+            HIP_OK(hipMemcpyAsync(p->d_op_engines, p->h_op_engines, sizeof(uint32_t) * pk.n_act, hipMemcpyHostToDevice, st));
+            owdev::k_apply_ops<<<dim3(pk.n_act), dim3(64), 0, st>>>(p->dK, p->d_nt, p->d_vrec, p->d_args, p->d_ops, p->d_op_engines, p->d_ops_fix);
         }
-        if (whole) p->dev_ops_pending = false;
+        if (b.whole) p->dev_ops_pending = false;
     }
     if (p->profiling) HIP_OK(hipEventRecord(p->ev[1], st));
-    const bool voices = with_voices && (any_main || any_steal);
-    if (voices) {
-        // the lists depend on masks, pending ops (any_dirty) and the transient flags of the previous block (post_render_host)
-        if (!p->lists_valid || any_dirty || p->lists_e0 != e0 || p->lists_ne != ne) build_voice_lists(p, e0, ne);
-        p->lists_valid = !any_dirty;     // engines with ops were classified "general" for this block only
+}
+
+// The voice kernels over the packed lists (build_voice_lists).  Returns whether a steady launch will report its jitter grids (d_skew_seen).
+static bool launch_voices(ow_pool* p, const Block& b) {
+    const int I = (int)p->I, L = b.L, Lcap = (int)p->Lcap;
+    hipStream_t s = p->stream;
+    const unsigned bs = p->vl_steady.n_blocks, bg = p->vl_general.n_blocks, bt = p->vl_steal.n_blocks, ba = p->vl_attack.n_blocks;
+    if (ba) owdev::k_voice_steady<false, 1><<<dim3(ba), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_attack.d, p->d_sum, p->d_eout, I, L, Lcap, nullptr);
+    if (bs) {
+        // voices on more than one jitter grid in some wavefront of the previous steady launch: the skewed variant (same samples)
+        if (p->sw.voice_skew && p->skew_next)
+            owdev::k_voice_steady<true><<<dim3(bs), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_steady.d, p->d_sum, p->d_eout, I, L, Lcap, p->d_skew_seen);
+        else
+            owdev::k_voice_steady<false><<<dim3(bs), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_steady.d, p->d_sum, p->d_eout, I, L, Lcap, p->d_skew_seen);
     }
-    // ---- stages (see ow_pool::slice_start).  Without voices the lists are not built: one stage.
-    const int NP = voices ? std::min(pipeline_stages(p, ne), p->slice_T) : 1;
-    const bool overlap = pipeline_overlap(p);
-    p->last_np = NP;
-    bool steady_launched = false;
-    if (voices && p->vl_steady.n_blocks) HIP_OK(hipMemsetAsync(p->d_skew_seen, 0, sizeof(uint32_t), st));
-    if (NP > 1) HIP_OK(hipEventRecord(p->ev_ready, st));      // args, ops and voice lists are in place
-    // A target inside a pinned block of ow_host_alloc is written by the output stage itself (it is mapped into the device's address space)
-    float* out_direct = nullptr;
-    if (out_host && p->sw.out_direct != 0 && out_stride >= len && ne > 0)
-        out_direct = (float*)host_block_device_ptr(out_host, sizeof(float) * ((size_t)(ne - 1) * out_stride + len));
-    for (int k = 0; k < NP; ++k) {
-        bool direct_done = false;
-        hipStream_t s = p->pipe_stream[k];                    // [0] == st
-        const int t0 = k * p->slice_T / NP, t1 = (k + 1) * p->slice_T / NP;
-        const int se0 = NP == 1 ? e0 : e0 + std::min(ne, t0 * p->slice_per);
-        const int se1 = NP == 1 ? e0 + ne : e0 + std::min(ne, t1 * p->slice_per);
-        const int sne = se1 - se0;
-        if (k > 0) {
-            HIP_OK(hipStreamWaitEvent(s, p->ev_ready, 0));
-            HIP_OK(hipStreamWaitEvent(s, p->ev_voice_done[k - 1], 0));   // the kernels of the stages run one stage after the other
-        }
-        if (p->profiling) HIP_OK(hipEventRecord(p->ev_stage[k][0], s));
-        if (voices) {
-            const ow_pool::SliceStart& a0 = p->slice_start[NP == 1 ? 0 : t0];
-            const ow_pool::SliceStart& a1 = p->slice_start[NP == 1 ? p->slice_T : t1];
-            const unsigned bs = (a1.s - a0.s) / 64, bg = (a1.g - a0.g) / 64, bt = (a1.t - a0.t) / 64, ba = (a1.a - a0.a) / 64;
-            if (ba) owdev::k_voice_steady<false, 1><<<dim3(ba), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_attack.d + a0.a, p->d_sum, p->d_eout, I, L, Lcap, nullptr);
-            if (bs)
-                {
-                // voices on more than one jitter grid in some wavefront of the previous steady launch: the skewed variant (same samples)
-                if (p->sw.voice_skew && p->skew_next)
-                    owdev::k_voice_steady<true><<<dim3(bs), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_steady.d + a0.s, p->d_sum, p->d_eout, I, L, Lcap, p->d_skew_seen);
-                else
-                    owdev::k_voice_steady<false><<<dim3(bs), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_steady.d + a0.s, p->d_sum, p->d_eout, I, L, Lcap, p->d_skew_seen);
-                steady_launched = true;
-            }
-            if (bg) {
-                // the release variant of the steady kernel takes the blocks whose voices are all past onset and noise (each block decides by
-                // itself, voice_steal_takes: what is left in this list are engines with a damping voice); k_voice (pass | 4) renders the others
-                const bool rel = p->sw.voice_release && !p->sw.force_general;      // (force_general measures k_voice itself)
-                if (rel) owdev::k_voice_steady<false, 3><<<dim3(bg), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_general.d + a0.g, p->d_sum, p->d_eout, I, L, Lcap, nullptr);
-                owdev::k_voice<<<dim3(bg), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_general.d + a0.g, p->d_sum, p->d_eout, I, L, Lcap, rel ? 4 : 0);
-            }
-            if (bt) {
-                // the steal variant of the steady kernel takes the engines whose steal voices are past onset and noise (each block decides
-                // by itself, voice_steal_takes); k_voice (pass | 4) renders the others
-                if (p->sw.voice_steal) owdev::k_voice_steady<false, 2><<<dim3(bt), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_steal.d + a0.t, p->d_sum, p->d_eout, I, L, Lcap, nullptr);
-                owdev::k_voice<<<dim3(bt), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_steal.d + a0.t, p->d_sum, p->d_eout, I, L, Lcap, p->sw.voice_steal ? 5 : 1);
-            }
-        }
-        if (overlap && k + 1 < NP) HIP_OK(hipEventRecord(p->ev_voice_done[k], s));
-        if (p->profiling) HIP_OK(hipEventRecord(p->ev_stage[k][1], s));
-        if (own_osc || hit) HIP_OK(hipStreamWaitEvent(s, p->ev_trem[rb_now_idx], 0));
-        if (traj_ready) HIP_OK(hipStreamWaitEvent(s, traj_ready, 0));
-        if (p->profiling) HIP_OK(hipEventRecord(p->ev_stage[k][2], s));
-        const bool fused = chain && sne > 0 && chain_fused(p, sne);
-        // k_chain_stream (ow_chain_stream.h): legacy preamp + behavioural amp, oversampled chain, pools too big for the quad kernels.
-        // Default: when the block goes to a pinned host block (the point of it: no copy trails the launch); OW_CHAIN_STREAM=1 always.
-        const bool streamed = chain && !fused && sne > 0 && p->hc.oversample && p->hc.preamp_kind == OW_PREAMP_LEGACY8 && p->power_amp_kind == OW_POWER_AMP_BEHAVIORAL &&
-                              !preamp_wide(p, sne) && (p->sw.chain_stream < 0 ? out_direct != nullptr : p->sw.chain_stream == 1);
-        if (fused && chain_row(p, sne)) {      // ... with one solver state per row of sixteen lanes (ow_chain_row.h): four preamp wavefronts + the output-stage one per eight engines
-            const dim3 gr((sne + 7) / 8), bl(320);
-            if (p->hc.oversample && L <= 128) owdev::k_chain_row<true, 8><<<gr, bl, 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, se0, sne);
-            else if (p->hc.oversample) owdev::k_chain_row<true, 16><<<gr, bl, 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, se0, sne);
-            else if (L <= 128) owdev::k_chain_row<false, 8><<<gr, bl, 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, se0, sne);
-            else owdev::k_chain_row<false, 16><<<gr, bl, 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, se0, sne);
-        } else if (fused) {    // small pool: preamp and output stage as two wavefronts of one workgroup (ow_chain_wide.h)
-            if (p->hc.oversample)
-                owdev::k_chain_fused<true><<<dim3((sne + 7) / 8), dim3(128), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, se0, sne);
-            else
-                owdev::k_chain_fused<false><<<dim3((sne + 7) / 8), dim3(128), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, se0, sne);
-        } else if (sne > 0 && chain && streamed) {   // big oversampled pool: preamp and output stage alternate per 64-sample chunk in one launch, rows stored
-            float* o2 = out_direct ? out_direct + (size_t)(se0 - e0) * out_stride : nullptr;      // straight into the caller's pinned block
-            owdev::k_chain_stream<<<dim3((sne + 31) / 32), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, se0, sne, o2, out_stride);
-            direct_done = o2 != nullptr;
-        } else if (sne > 0 && chain) {
-            if (p->hc.preamp_kind == OW_PREAMP_MELANGE12 && !melange_rank_one(p) && p->hc.ml_sparse_ok && !melange_lds_matrix(p) && melange_lane_engine(p, sne))
-                owdev::k_preamp_mel_eng<<<dim3((sne + 63) / 64), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_mel_settled, p->d_args, p->d_eout, p->d_sum, tsrc,
-                                                                                 p->d_pre, p->d_noise, I, L, Lcap, se0, sne, melange_generic_only(p) ? 1 : 0,
-                                                                                 p->d_mel_lu, p->mel_lu_ld);
-            else if (p->hc.preamp_kind == OW_PREAMP_MELANGE12 && !melange_rank_one(p) && p->hc.ml_sparse_ok && !melange_lds_matrix(p))
-                owdev::k_preamp_mel_col<<<dim3((sne + 31) / 32), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_mel_settled, p->d_args, p->d_eout, p->d_sum, tsrc,
-                                                                                 p->d_pre, p->d_noise, I, L, Lcap, se0, sne, melange_generic_only(p) ? 1 : 0,
-                                                                                 p->d_mel_lu, p->mel_lu_ld);
-            else if (p->hc.preamp_kind == OW_PREAMP_MELANGE12 && !melange_rank_one(p))
-                owdev::k_preamp_mel_lit<<<dim3((sne + 31) / 32), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_mel_settled, p->d_args, p->d_eout, p->d_sum, tsrc,
-                                                                                 p->d_pre, p->d_noise, I, L, Lcap, se0, sne, melange_generic_only(p) ? 1 : 0, p->d_mel_lu);
-            else if (p->hc.preamp_kind == OW_PREAMP_MELANGE12)
-                owdev::k_preamp_mel<<<dim3((sne + 31) / 32), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_mel_settled, p->d_args, p->d_eout, p->d_sum, tsrc,
-                                                                             p->d_pre, p->d_noise, I, L, Lcap, se0, sne);
-            else if (preamp_wide(p, sne))
-                owdev::k_preamp_wide<<<dim3((sne + 7) / 8), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, se0, sne);
-            else if (p->sw.preamp_pair < 0 ? sne >= 131072 : p->sw.preamp_pair == 1)     // lane = engine: half the wavefronts, two per SIMD from 131 072 engines
-                owdev::k_preamp_pair<<<dim3((sne + 63) / 64), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, se0, sne);
-            else
-                owdev::k_preamp<<<dim3((sne + 31) / 32), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, se0, sne);
-        }
-        if (p->profiling) HIP_OK(hipEventRecord(p->ev_stage[k][3], s));
-        if (!chain || fused || streamed) {
-            // voice sums only / the output stage ran inside k_chain_fused or k_chain_stream
-        } else if (sne > 0 && p->power_amp_kind == OW_POWER_AMP_MELANGE) {
-            // more engines than one workgroup: dispatch them by falling demand of their last block (see k_post_mpa)
-            // -- when the block has more engines than the chip holds at once (two workgroups of 32 per CU); below that every wavefront
-            // is resident from the start, the block lasts as long as its slowest engine and the order cannot matter
-            const bool ordered = power_amp_ordered(p) && ne > power_amp_resident_engines(p);
-            if (ordered) {
-                uint32_t* hist = p->d_pa_hist + (size_t)k * PA_ORDER_CLASSES;
-                const uint32_t total = (uint32_t)L * (p->hc.oversample ? 2u : 1u);
-                HIP_OK(hipMemsetAsync(hist, 0, sizeof(uint32_t) * PA_ORDER_CLASSES, s));
-                owdev::k_pa_order_hist<<<dim3((sne + 255) / 256), dim3(256), 0, s>>>(p->d_pa_demand, se0, sne, total, hist);
-                owdev::k_pa_order_scan<<<dim3(1), dim3(PA_ORDER_CLASSES), 0, s>>>(hist);
-                owdev::k_pa_order_scatter<<<dim3((sne + 255) / 256), dim3(256), 0, s>>>(p->d_pa_demand, se0, sne, total, hist, p->d_pa_order);
-            }
-            owdev::k_post_mpa<<<dim3((sne + PA_EPB - 1) / PA_EPB), dim3(PA_WPB * 64), 0, s>>>(p->dK, p->dPa, p->d_pa_settled, p->d_cs, p->d_pa, p->d_args, p->d_eout, p->d_pre, p->d_out,
-                                                                          p->d_pa_tap, I, L, L, se0, sne, ordered ? p->d_pa_order : nullptr, p->d_pa_demand);
-        } else if (sne > 0) {
-            float* o2 = out_direct ? out_direct + (size_t)(se0 - e0) * out_stride : nullptr;
-            if (p->hc.oversample && (p->sw.post_pair < 0 ? sne >= 131072 : p->sw.post_pair == 1))
-                owdev::k_post<false, true><<<dim3((sne + 63) / 64), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_pre, p->d_out, I, L, L, se0, sne, o2, out_stride);
-            else if (p->hc.oversample)
-                owdev::k_post<true><<<dim3((sne + 31) / 32), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_pre, p->d_out, I, L, L, se0, sne, o2, out_stride);
-            else
-                owdev::k_post<false><<<dim3((sne + 63) / 64), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_pre, p->d_out, I, L, L, se0, sne, o2, out_stride);
-            direct_done = o2 != nullptr;
-        }
-        if (p->profiling) HIP_OK(hipEventRecord(p->ev_stage[k][4], s));
-        if (!overlap && k + 1 < NP) HIP_OK(hipEventRecord(p->ev_voice_done[k], s));   // the next stage computes while this one's rows are copied
-        if (out_host && sne > 0 && !direct_done) {        // the stage's rows go out while the later stages still compute
-            float* dst = out_host + (size_t)(se0 - e0) * out_stride;
-            const float* src = p->d_out + (size_t)se0 * len;
-            if (out_stride == len) HIP_OK(hipMemcpyAsync(dst, src, sizeof(float) * len * (size_t)sne, hipMemcpyDeviceToHost, s));
-            else HIP_OK(hipMemcpy2DAsync(dst, out_stride * sizeof(float), src, len * sizeof(float), len * sizeof(float), (size_t)sne, hipMemcpyDeviceToHost, s));
-        }
-        if (k > 0) HIP_OK(hipEventRecord(p->ev_stage_done[k], s));
+    if (bg) {
+        // the release variant of the steady kernel takes the blocks whose voices are all past onset and noise (each block decides by
+        // itself, voice_steal_takes: what is left in this list are engines with a damping voice); k_voice (pass | 4) renders the others
+        const bool rel = p->sw.voice_release && !p->sw.force_general;      // (force_general measures k_voice itself)
+        if (rel) owdev::k_voice_steady<false, 3><<<dim3(bg), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_general.d, p->d_sum, p->d_eout, I, L, Lcap, nullptr);
+        owdev::k_voice<<<dim3(bg), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_general.d, p->d_sum, p->d_eout, I, L, Lcap, rel ? 4 : 0);
     }
-    for (int k = 1; k < NP; ++k) HIP_OK(hipStreamWaitEvent(st, p->ev_stage_done[k], 0));
-    if (chain && p->traj) {          // the engines of the range are n_os samples further along the trajectory
-        if (whole) p->trem_clock += n_os;
+    if (bt) {
+        // the steal variant of the steady kernel takes the engines whose steal voices are past onset and noise (each block decides
+        // by itself, voice_steal_takes); k_voice (pass | 4) renders the others
+        if (p->sw.voice_steal) owdev::k_voice_steady<false, 2><<<dim3(bt), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_steal.d, p->d_sum, p->d_eout, I, L, Lcap, nullptr);
+        owdev::k_voice<<<dim3(bt), dim3(64), 0, s>>>(p->dK, p->d_vrec, p->vl_steal.d, p->d_sum, p->d_eout, I, L, Lcap, p->sw.voice_steal ? 5 : 1);
+    }
+    return bs != 0;
+}
+
+// Voice sums -> preamp rows, or (CHAIN_*) -> finished rows.  Returns whether the rows went straight into the caller's pinned block.
+static bool launch_chain(ow_pool* p, const Block& b, ChainKernel kernel) {
+    const int I = (int)p->I, L = b.L, Lcap = (int)p->Lcap, e0 = b.e0, ne = b.ne;
+    hipStream_t s = p->stream;
+    const owdev::OwTremSrc& tsrc = b.tsrc;
+    const dim3 per8((ne + 7) / 8), per32((ne + 31) / 32), per64((ne + 63) / 64);
+    const int generic = p->sw.mel_generic ? 1 : 0;
+    switch (kernel) {
+    case CHAIN_NONE: break;
+    case CHAIN_ROW_OS_8: owdev::k_chain_row<true, 8><<<per8, dim3(320), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, e0, ne); break;
+    case CHAIN_ROW_OS_16: owdev::k_chain_row<true, 16><<<per8, dim3(320), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, e0, ne); break;
+    case CHAIN_ROW_8: owdev::k_chain_row<false, 8><<<per8, dim3(320), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, e0, ne); break;
+    case CHAIN_ROW_16: owdev::k_chain_row<false, 16><<<per8, dim3(320), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, e0, ne); break;
+    case CHAIN_FUSED_OS: owdev::k_chain_fused<true><<<per8, dim3(128), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, e0, ne); break;
+    case CHAIN_FUSED: owdev::k_chain_fused<false><<<per8, dim3(128), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, e0, ne); break;
+    case CHAIN_STREAM:
+        owdev::k_chain_stream<<<per32, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_out, I, L, Lcap, L, e0, ne, b.out_direct, b.out_stride);
+        return b.out_direct != nullptr;
+    case PREAMP_MEL_ENG:
+        owdev::k_preamp_mel_eng<<<per64, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_mel_settled, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_noise, I, L, Lcap, e0, ne, generic, p->d_mel_lu, p->mel_lu_ld);
+        break;
+    case PREAMP_MEL_COL:
+        owdev::k_preamp_mel_col<<<per32, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_mel_settled, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_noise, I, L, Lcap, e0, ne, generic, p->d_mel_lu, p->mel_lu_ld);
+        break;
+    case PREAMP_MEL_LIT:
+        owdev::k_preamp_mel_lit<<<per32, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_mel_settled, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_noise, I, L, Lcap, e0, ne, generic, p->d_mel_lu);
+        break;
+    case PREAMP_MEL: owdev::k_preamp_mel<<<per32, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_mel_settled, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_noise, I, L, Lcap, e0, ne); break;
+    case PREAMP_WIDE: owdev::k_preamp_wide<<<per8, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, e0, ne); break;
+    case PREAMP_PAIR: owdev::k_preamp_pair<<<per64, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, e0, ne); break;
+    case PREAMP_LANE: owdev::k_preamp<<<per32, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, e0, ne); break;
+    }
+    return false;
+}
+
+// Preamp rows -> finished rows.  Returns whether they went straight into the caller's pinned block.
+static bool launch_output_stage(ow_pool* p, const Block& b, PostKernel kernel) {
+    const int I = (int)p->I, L = b.L, e0 = b.e0, ne = b.ne;
+    hipStream_t s = p->stream;
+    switch (kernel) {
+    case POST_NONE: return false;                // voice sums only / the output stage ran inside the chain kernel
+    case POST_MPA: {
+        // more engines than the chip holds at once: dispatch them by falling demand of their last block (see k_post_mpa); below that every
+        // wavefront is resident from the start, the block lasts as long as its slowest engine and the order cannot matter
+        const bool ordered = p->sw.pa_sort != 0 && ne > power_amp_resident_engines(p);
+        if (ordered) {
+            const uint32_t total = (uint32_t)b.n_os;
+            HIP_OK(hipMemsetAsync(p->d_pa_hist, 0, sizeof(uint32_t) * PA_ORDER_CLASSES, s));
+            owdev::k_pa_order_hist<<<dim3((ne + 255) / 256), dim3(256), 0, s>>>(p->d_pa_demand, e0, ne, total, p->d_pa_hist);
+            owdev::k_pa_order_scan<<<dim3(1), dim3(PA_ORDER_CLASSES), 0, s>>>(p->d_pa_hist);
+            owdev::k_pa_order_scatter<<<dim3((ne + 255) / 256), dim3(256), 0, s>>>(p->d_pa_demand, e0, ne, total, p->d_pa_hist, p->d_pa_order);
+        }
+        owdev::k_post_mpa<<<dim3((ne + PA_EPB - 1) / PA_EPB), dim3(PA_WPB * 64), 0, s>>>(p->dK, p->dPa, p->d_pa_settled, p->d_cs, p->d_pa, p->d_args, p->d_eout, p->d_pre, p->d_out,
+                                                                                     p->d_pa_tap, I, L, L, e0, ne, ordered ? p->d_pa_order : nullptr, p->d_pa_demand);
+        return false;
+    }
+    case POST_PAIR: owdev::k_post<false, true><<<dim3((ne + 63) / 64), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_pre, p->d_out, I, L, L, e0, ne, b.out_direct, b.out_stride); break;
+    case POST_OS: owdev::k_post<true><<<dim3((ne + 31) / 32), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_pre, p->d_out, I, L, L, e0, ne, b.out_direct, b.out_stride); break;
+    case POST_BASE: owdev::k_post<false><<<dim3((ne + 63) / 64), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_pre, p->d_out, I, L, L, e0, ne, b.out_direct, b.out_stride); break;
+    }
+    return b.out_direct != nullptr;
+}
+
+// the block's rows to the caller's host buffer, unless the output stage stored them there itself
+static void deliver_rows(ow_pool* p, const Block& b) {
+    const float* src = p->d_out + (size_t)b.e0 * b.len;
+    if (b.out_stride == b.len) HIP_OK(hipMemcpyAsync(b.out_host, src, sizeof(float) * b.len * (size_t)b.ne, hipMemcpyDeviceToHost, p->stream));
+    else HIP_OK(hipMemcpy2DAsync(b.out_host, b.out_stride * sizeof(float), src, b.len * sizeof(float), b.len * sizeof(float), (size_t)b.ne, hipMemcpyDeviceToHost, p->stream));
+}
+
+// the trajectory clock, the steady launch's report and the block's status on their way to the host (post_render_host reads them after the sync)
+static void finish_block(ow_pool* p, const Block& b, bool steady_launched) {
+    const int e0 = b.e0, ne = b.ne, n_os = b.n_os;
+    hipStream_t st = p->stream;
+    if (b.chain && p->traj) {          // the engines of the range are n_os samples further along the trajectory
+        if (b.whole) p->trem_clock += n_os;
         else {
             for (int k = 0; k < ne; ++k) if (p->h_birth[e0 + k] != OW_OFF_TRAJ) { p->h_birth[e0 + k] -= n_os; p->min_birth = std::min(p->min_birth, p->h_birth[e0 + k]); }
             owdev::k_trem_birth_shift<<<dim3((ne + 255) / 256), dim3(256), 0, st>>>(p->d_birth, e0, ne, -(long long)n_os);
@@ -752,6 +773,55 @@ void render_range(ow_pool* p, int e0, int ne, size_t len, bool with_voices, floa
         HIP_OK(hipMemcpyAsync(p->h_eout + e0, p->d_eout + e0, sizeof(OwEngineOut) * ne, hipMemcpyDeviceToHost, st));
         p->attn_pending = false;
     }
+}
+
+// One render of `len` samples for engines [e0, e0+ne).  with_voices=false skips the voice kernels
+// (warm-up of engines whose voices were just freed).
+// out_host != nullptr: rows [e0, e0+ne) of the block are copied to out_host[(e - e0) * out_stride].
+void render_range(ow_pool* p, int e0, int ne, size_t len, bool with_voices, float* out_host = nullptr, size_t out_stride = 0) {
+    if (len > p->Lcap) { HIP_OK(hipStreamSynchronize(p->stream)); alloc_stream_buffers(p, len); }  // auto-grow, engine.rs:430 (also after a grow that failed: Lcap 0)
+    p->out_ld = len;
+    hipStream_t st = p->stream;
+    auto profile_mark = [&](int i) { if (p->profiling) HIP_OK(hipEventRecord(p->ev_stage[i], st)); };
+    vm_wait_download(p);                     // a burst applied on the device: the host's copy of the voice-pool states is complete from here on
+    Block b;
+    b.e0 = e0; b.ne = ne; b.len = len; b.L = (int)len; b.n_os = b.L * (p->hc.oversample ? 2 : 1);
+    b.whole = e0 == 0 && ne == (int)p->I;
+    b.chain = !p->voices_only;
+    b.out_host = out_host; b.out_stride = out_stride;
+    b.tsrc = owdev::OwTremSrc{nullptr, p->d_lead, nullptr, p->d_birth};
+    // ---- tremolo: CdS cell resistance of this block, from the shared trajectory and / or the pool's own oscillators
+    const hipEvent_t traj_ready = b.chain && p->traj ? traj_cover_block(p, b) : nullptr;
+    const int trem_half = trem_block(p, b);
+    // ---- host state of the engines -> device
+    const Packed pk = pack_args_and_ops(p, b);
+    upload_and_apply_ops(p, b, pk);
+    // ---- voices
+    const bool voices = with_voices && (pk.any_main || pk.any_steal);
+    if (voices) {
+        // the lists depend on masks, pending ops (any_dirty) and the transient flags of the previous block (post_render_host)
+        if (!p->lists_valid || pk.any_dirty || p->lists_e0 != e0 || p->lists_ne != ne) build_voice_lists(p, e0, ne);
+        p->lists_valid = !pk.any_dirty;     // engines with ops were classified "general" for this block only
+        if (p->vl_steady.n_blocks) HIP_OK(hipMemsetAsync(p->d_skew_seen, 0, sizeof(uint32_t), st));
+    }
+    // A target inside a pinned block of ow_host_alloc is written by the output stage itself (it is mapped into the device's address space)
+    if (out_host && p->sw.out_direct != 0 && out_stride >= len && ne > 0)
+        b.out_direct = (float*)host_block_device_ptr(out_host, sizeof(float) * ((size_t)(ne - 1) * out_stride + len));
+    profile_mark(0);
+    const bool steady_launched = voices && launch_voices(p, b);
+    profile_mark(1);
+    // ---- chain: preamp and output stage, once this block's R_ldr is there
+    if (trem_half >= 0) HIP_OK(hipStreamWaitEvent(st, p->ev_trem[trem_half], 0));
+    if (traj_ready) HIP_OK(hipStreamWaitEvent(st, traj_ready, 0));
+    profile_mark(2);
+    const ChainKernel chain = !b.chain ? CHAIN_NONE
+        : choose_chain(p->sw, (int)p->hc.preamp_kind, p->power_amp_kind, p->hc.oversample != 0, p->hc.ml_sparse_ok != 0, ne, b.L, b.out_direct != nullptr);
+    bool delivered = launch_chain(p, b, chain);
+    profile_mark(3);
+    delivered |= launch_output_stage(p, b, choose_post(p->sw, p->power_amp_kind, p->hc.oversample != 0, ne, chain));
+    profile_mark(4);
+    if (out_host && ne > 0 && !delivered) deliver_rows(p, b);
+    finish_block(p, b, steady_launched);
 }
 
 // host bookkeeping of ONE engine after a block: steal-fade countdown (engine.rs:490-493), NaN-guard frees (engine.rs:499-521,
@@ -962,15 +1032,9 @@ void collect_profile(ow_pool* p) {
     else hipEventSynchronize(p->ev[7]);   // in a small pool the block-ahead tremolo outlasts the audio stream; profiling waits for it, a normal render does not
     hipEventElapsedTime(&p->last_ms[0], p->ev[0], p->ev[1]);   // ops
     if (!p->voices_only) hipEventElapsedTime(&p->last_ms[2], p->ev[6], p->ev[7]);   // tremolo (own stream)
-    // per-stage intervals on the stage streams, summed: voices run one stage after the other (the sum is the voice kernels' time, with
-    // the previous stage's chain kernels running beside them); preamp / post of a stage overlap the next stage's voices
-    float v = 0.f, pr = 0.f, po = 0.f, x = 0.f;
-    for (int k = 0; k < p->last_np; ++k) {
-        hipEventElapsedTime(&x, p->ev_stage[k][0], p->ev_stage[k][1]); v += x;
-        hipEventElapsedTime(&x, p->ev_stage[k][2], p->ev_stage[k][3]); pr += x;
-        hipEventElapsedTime(&x, p->ev_stage[k][3], p->ev_stage[k][4]); po += x;
-    }
-    p->last_ms[1] = v; p->last_ms[3] = pr; p->last_ms[4] = po;
+    hipEventElapsedTime(&p->last_ms[1], p->ev_stage[0], p->ev_stage[1]);   // voices
+    hipEventElapsedTime(&p->last_ms[3], p->ev_stage[2], p->ev_stage[3]);   // preamp (or the whole chain kernel)
+    hipEventElapsedTime(&p->last_ms[4], p->ev_stage[3], p->ev_stage[4]);   // output stage
 }
 
 // WurliEngine::warm_up (engine.rs:261-270): 0.6 s of render() in 512-sample blocks
@@ -1012,17 +1076,11 @@ ow_pool* pool_create(double sample_rate, size_t n_engines, int device, int pream
     p->power_amp_kind = power_amp_kind;
     p->tremolo_kind = tremolo_kind;
     p->voices_only = voices_only;
-    p->pipe_stream[0].create();
-    p->stream = p->pipe_stream[0];
+    p->stream.create();             // main, tremolo, copy: see ow_pool::stream
     p->stream_trem.create();
+    p->stream_copy.create();
     for (auto& e : p->ev) e.create(hipEventDefault);
-    for (int k = 1; k < OW_MAX_STAGES; ++k) p->pipe_stream[k].create();
-    p->ev_ready.create();
-    for (int k = 0; k < OW_MAX_STAGES; ++k) {
-        p->ev_voice_done[k].create();
-        p->ev_stage_done[k].create();
-        for (auto& e : p->ev_stage[k]) e.create(hipEventDefault);
-    }
+    for (auto& e : p->ev_stage) e.create(hipEventDefault);
     for (auto& e : p->ev_trem) e.create();
     p->d_trem_backup.alloc(18 * n_engines);
     p->d_trem_settled.alloc(18);
@@ -1083,7 +1141,7 @@ ow_pool* pool_create(double sample_rate, size_t n_engines, int device, int pream
         p->d_pa_demand.alloc(n_engines);
         HIP_OK(hipMemsetAsync(p->d_pa_demand, 0, sizeof(uint32_t) * n_engines, p->stream));
         p->d_pa_order.alloc(n_engines);
-        p->d_pa_hist.alloc(PA_ORDER_CLASSES * OW_MAX_STAGES);
+        p->d_pa_hist.alloc(PA_ORDER_CLASSES);
     }
     upload_consts(p, sample_rate, preamp_kind);
     owdev::k_note_table<<<dim3(1), dim3(64), 0, p->stream>>>(p->d_nt);

@@ -147,6 +147,6 @@ TremSettled trem_settled_rows(int device, double os_sr, const OwConsts* dK, cons
 ow_pool::~ow_pool() {      // also of a pool that pool_create gave up half-way: whatever exists is drained, then the members release themselves
     hipSetDevice(device);
     if (stream) hipStreamSynchronize(stream);
-    invalidate_spec(this);
-    for (int k = 1; k < OW_MAX_STAGES; ++k) if (pipe_stream[k]) hipStreamSynchronize(pipe_stream[k]);
+    invalidate_spec(this);                                   // (drains the tremolo stream)
+    if (stream_copy) hipStreamSynchronize(stream_copy);
 }

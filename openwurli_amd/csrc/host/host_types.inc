@@ -43,9 +43,11 @@ struct ow_pool {
     OwConsts hc{};
     // Every device resource below is an owning member (host_base.inc) and releases itself in ~ow_pool, in reverse order of declaration:
     // the streams come first so that they go last, after every buffer and event.
-    hipStream_t stream = nullptr;      // voices -> preamp -> output stage; == pipe_stream[0], which owns it
+    // Created in this order (pool_create): the runtime deals streams onto the hardware queues in creation order, and the oscillator must
+    // not share a queue with the audio stream.
+    StreamOwner stream;                // voices -> preamp -> output stage
     StreamOwner stream_trem;           // tremolo oscillator: no audio input (tremolo.rs:121), runs beside the voices
-    StreamOwner pipe_stream[OW_MAX_STAGES];   // stage streams of the staged render, below
+    StreamOwner stream_copy;           // copies beside the kernels: state download of a device MIDI burst, background state upload after a block
     Event ev_trem[2];                  // one per rbuf half
     // The tremolo oscillator is produced one block ahead (speculating that the next block has the same length); the
     // tremolo rows of the chain state are backed up first so a mis-speculation can be rolled back.
@@ -65,7 +67,7 @@ struct ow_pool {
     DevBuf<double> d_pa_tap;          // test tap: amp output per chain-rate sample, [2 * Lcap][I] (ow_test_pool_enable_power_amp_tap)
     DevBuf<uint32_t> d_pa_demand;     // [I] Newton passes of the engine's last block (k_post_mpa), 0 = not rendered yet
     DevBuf<uint32_t> d_pa_order;      // [I] engines of a launch range by falling demand (k_pa_order_*)
-    DevBuf<uint32_t> d_pa_hist;       // [OW_MAX_STAGES][256] class counts / cursors of the ranges
+    DevBuf<uint32_t> d_pa_hist;       // [256] class counts / cursors of the range
     size_t pa_tap_cap = 0;
     DevBuf<double> d_mel_settled;     // melange preamp: settled codegen-rate state (18 doubles)
     size_t mel_lu_ld = 0;             // column-streamed literal kernel: lanes per row of d_mel_lu
@@ -145,14 +147,7 @@ struct ow_pool {
     std::vector<uint8_t> transient;   // per engine: device status after the previous block (OwEngineOut::transient)
     bool lists_valid = false;
     int lists_e0 = -1, lists_ne = -1;
-    // Staged render (render_range), used when a big pool's block is copied to the host: the range is cut into NP engine stages, each
-    // on its own stream; the kernels of stage k start when those of stage k-1 have finished, so the device-to-host copy of stage k-1
-    // (copy engine) runs beside the kernels of stage k.  Stage boundaries are slice boundaries of the packed voice lists.
-    int slice_T = 1, slice_per = 0;                             // slices the lists were packed in, engines per slice
-    struct SliceStart { uint32_t s = 0, g = 0, t = 0, a = 0; uint64_t h[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}}; } slice_start[OW_MAX_SLICES + 1];   // entry offsets of every slice in the four lists (h: pass-1 hashes of a slice, unused in the stored copy)
-    Event ev_ready, ev_voice_done[OW_MAX_STAGES], ev_stage_done[OW_MAX_STAGES];
-    Event ev_stage[OW_MAX_STAGES][5];                          // profiling: before voices, after voices, before preamp, after preamp, after post
-    int last_np = 1;
+    Event ev_stage[5];                // profiling: before voices, after voices, before preamp, after preamp, after post
     DevBuf<uint32_t> d_op_engines;    // engines that have pending ops this block (k_apply_ops runs one block per entry)
     PinBuf<uint32_t> h_op_engines;    // pinned, I entries
     std::vector<std::unique_ptr<ow_engine>> engines;   // the C-ABI hands out the (stable) ow_engine* inside

@@ -1,11 +1,14 @@
 // openwurli-hip: host side of the C-ABI (include/openwurli_hip.h) -- pool/engine objects,
 // the voice-pool / MIDI state machine of WurliEngine (engine.rs:299-374,569-602) and the
-// kernel launch sequence of one render.  The state machine is integer/branchy host work;
+// kernel launch sequence of one render (host_pool.inc: render_range, a sequence of named
+// phases; which chain / output-stage kernel a block gets is decided by the pure functions
+// choose_chain / choose_post there).  The state machine is integer/branchy host work;
 // everything that touches audio samples runs in the gfx950 kernels of ow_kernels.h.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -54,13 +57,13 @@ using owdev::OwEngineOut;
 
 // The host side is ONE translation unit cut along its seams (round 6: 4 200 lines in one file before); every piece is included here, in
 // dependency order, and nowhere else.
-#include "host/host_base.inc"           // errors, device buffers, persistent host workers, latched switches
+#include "host/host_base.inc"           // errors, device buffers, persistent host workers, latched switches and their one table
 #include "host/host_types.inc"          // ow_engine / ow_pool: the host side of one engine and of a pool
 #include "host/host_settle.inc"         // voice-pool mirror synchronisation, process-wide settled states (melange preamp / power amp, Twin-T)
 #include "host/host_trajectory.inc"     // the shared Twin-T / CdS trajectory store (TremTraj), its helper thread, traj_acquire
 #include "host/host_offline.inc"        // what the offline entry points share: refusals, row geometry and chunking, OfflineCall, the melange power amp stage
 #include "host/host_jobs_chain.inc"     // kernel choice for the job paths and the job chain (batch render, render-midi)
-#include "host/host_pool.inc"           // tremolo phase groups, chain (re)initialisation, voice lists, render_range, post-render bookkeeping, pool life cycle
+#include "host/host_pool.inc"           // tremolo phase groups, chain (re)initialisation, kernel choice of a block, voice lists, render_range and its phases, post-render bookkeeping, pool life cycle
 #include "host/api_pool.inc"            // C-ABI: library / pool entry points, host blocks, taps, trajectory control and persistence, MIDI bursts
 #include "host/api_engines.inc"         // C-ABI: the WurliEngine API (engine.rs)
 #include "host/api_test_hooks.inc"      // C-ABI of include/openwurli_hip_test.h: host-logic hooks, diagnostics, switches
