@@ -526,25 +526,50 @@ extern __device__ unsigned long long g_ow_dbg[8];      // (ow_melange_dev.h)
 // (x * log2(e) rounded to n, two-step reduction by ln 2, degree-11 polynomial, ldexp) without its overflow / underflow selects
 // (two compares, three v_cndmask), which cannot fire here.  Same constants, same operations: bit-identical to exp() on the whole
 // clamp range (tests/test_gpu_division.py::test_bounded_exp_is_the_library_exp).
+// (exp_core: the part both forms share.  F3: its polynomial steps as three-address v_fma_f64 (fma3) -- for the power amp, whose loop
+// keeps the coefficients in vector registers.  The junction laws keep the compiler's selection: the unrolled Newton loops of the preamp
+// step set their coefficients up with s_mov per use, where the same steps with the addend read from a scalar register measured
+// 0.03 ms of k_preamp_pair's 4.7, inside the run-to-run spread (profiles/chain_consts_bench.md); and the compiler prices an asm statement
+// like a call, so the kernels that unroll around dk_step by its estimate stop doing so with one inside.)
+template <bool F3>
+OW_DEV double exp_core(double x) {
+    const double n = rint(x * __longlong_as_double(0x3ff71547652b82feLL));
+    double r = __builtin_fma(__longlong_as_double((long long)0xbfe62e42fefa39efULL), n, x);
+    r = __builtin_fma(__longlong_as_double((long long)0xbc7abc9e3b39803fULL), n, r);
+#define OW_EXP_STEP(c) p = F3 ? fma3(r, p, __longlong_as_double(c)) : __builtin_fma(r, p, __longlong_as_double(c))
+    const double c11 = __longlong_as_double(0x3e5ade156a5dcb37LL), c10 = __longlong_as_double(0x3e928af3fca7ab0cLL);
+    double p = F3 ? fma3(c11, r, c10) : __builtin_fma(c11, r, c10);
+    OW_EXP_STEP(0x3ec71dee623fde64LL);
+    OW_EXP_STEP(0x3efa01997c89e6b0LL);
+    OW_EXP_STEP(0x3f2a01a014761f6eLL);
+    OW_EXP_STEP(0x3f56c16c1852b7b0LL);
+    OW_EXP_STEP(0x3f81111111122322LL);
+    OW_EXP_STEP(0x3fa55555555502a1LL);
+    OW_EXP_STEP(0x3fc5555555555511LL);
+    OW_EXP_STEP(0x3fe000000000000bLL);
+#undef OW_EXP_STEP
+    p = __builtin_fma(r, p, 1.0);
+    p = __builtin_fma(r, p, 1.0);
+    return ldexp(p, (int)n);
+}
 OW_DEV double exp_bounded(double x) {
 #ifdef OW_LIB_EXP
     return exp(x);
 #else
-    const double n = rint(x * __longlong_as_double(0x3ff71547652b82feLL));
-    double r = __builtin_fma(__longlong_as_double((long long)0xbfe62e42fefa39efULL), n, x);
-    r = __builtin_fma(__longlong_as_double((long long)0xbc7abc9e3b39803fULL), n, r);
-    double p = __builtin_fma(__longlong_as_double(0x3e5ade156a5dcb37LL), r, __longlong_as_double(0x3e928af3fca7ab0cLL));
-    p = __builtin_fma(r, p, __longlong_as_double(0x3ec71dee623fde64LL));
-    p = __builtin_fma(r, p, __longlong_as_double(0x3efa01997c89e6b0LL));
-    p = __builtin_fma(r, p, __longlong_as_double(0x3f2a01a014761f6eLL));
-    p = __builtin_fma(r, p, __longlong_as_double(0x3f56c16c1852b7b0LL));
-    p = __builtin_fma(r, p, __longlong_as_double(0x3f81111111122322LL));
-    p = __builtin_fma(r, p, __longlong_as_double(0x3fa55555555502a1LL));
-    p = __builtin_fma(r, p, __longlong_as_double(0x3fc5555555555511LL));
-    p = __builtin_fma(r, p, __longlong_as_double(0x3fe000000000000bLL));
-    p = __builtin_fma(r, p, 1.0);
-    p = __builtin_fma(r, p, 1.0);
-    return ldexp(p, (int)n);
+    return exp_core<false>(x);
+#endif
+}
+// exp() for any argument (the power amp's crossover term, whose argument reaches -3e6): exp_core behind the library's two selects,
+// +inf above 1024 and 0 below -1075 (a NaN passes both), which is the device library's f64 exp operation for operation -- the same bits
+// at every argument (tests/test_gpu_power_amp_cases.py pins them against a build that called the library).
+OW_DEV double exp_any(double x) {
+#ifdef OW_LIB_EXP
+    return exp(x);
+#else
+    double z = exp_core<true>(x);
+    z = x > 1024.0 ? __longlong_as_double(0x7ff0000000000000LL) : z;
+    z = x < -1075.0 ? 0.0 : z;
+    return z;
 #endif
 }
 // vbe.clamp(-1.0, VBE_MAX) as v_max_f64 + v_min_f64 (the compare-and-select form is two compares and four v_cndmask per junction).  The
@@ -705,16 +730,58 @@ __device__ inline double dk_step(DkSt& st, double input, double g_ldr, double g_
 // The two Newton loops run as ONE wave-uniform loop (two independent dependency chains per lane) that ends when every state of the
 // wavefront is done; a state that is done is no longer moved and its further evaluations repeat its last one bit for bit, exactly as
 // in dk_step.
-OW_DEV void dk_rhs(const double (*__restrict__ an)[8], const DkSt& st, double input, double g_ldr_prev, double p_g_cin, double rhs[8], double& cin_now) {
-    const double* v = st.v;
-    rhs[0] = an[0][0] * v[0] + an[0][2] * v[2];
-    rhs[1] = an[1][1] * v[1] + an[1][7] * v[7];
-    rhs[2] = an[2][0] * v[0] + an[2][2] * v[2] + an[2][5] * v[5];
-    rhs[3] = an[3][3] * v[3] + an[3][4] * v[4];
-    rhs[4] = an[4][3] * v[3] + an[4][4] * v[4];
-    rhs[5] = an[5][2] * v[2] + an[5][5] * v[5] + an[5][6] * v[6];
-    rhs[6] = an[6][5] * v[5] + an[6][6] * v[6] + an[6][7] * v[7];
-    rhs[7] = an[7][1] * v[1] + an[7][6] * v[6] + an[7][7] * v[7];
+// DkPairRes: the wave-uniform constants that dk_step_pair keeps RESIDENT in vector registers for the whole block instead of fetching them
+// again through the scalar cache in every chain sample: the 20 structural non-zeros of A_neg (row by row, dk_step's order), 2w and the
+// feedback column of S -- 36 doubles in the 76 registers k_preamp_pair leaves free at two wavefronts per SIMD.  Each of their fetch
+// groups was an s_load the sample loop waited for a few instructions later; what is left for the scalar side (S, K', the closing column
+// differences) then fits the scalar file better.  The empty asm keeps a value opaque, so the compiler cannot turn it back into a scalar
+// fetch inside the loop.  The same constants in the same operations: the same bits.
+struct DkPairRes { double an[20], two_w[8], s_fb_col[8], g_cin; };
+__device__ inline void dk_pair_res_load(DkPairRes& R, const OwConsts* __restrict__ K) {
+    const double (*__restrict__ an)[8] = K->p_a_neg;
+    const double a[20] = {an[0][0], an[0][2], an[1][1], an[1][7], an[2][0], an[2][2], an[2][5], an[3][3], an[3][4], an[4][3],
+                          an[4][4], an[5][2], an[5][5], an[5][6], an[6][5], an[6][6], an[6][7], an[7][1], an[7][6], an[7][7]};
+#pragma unroll
+    for (int i = 0; i < 20; ++i) { double x = a[i]; asm volatile("" : "+v"(x)); R.an[i] = x; }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        double w = K->p_two_w[i], c = K->p_s_fb_col[i];
+        asm volatile("" : "+v"(w));
+        asm volatile("" : "+v"(c));
+        R.two_w[i] = w; R.s_fb_col[i] = c;
+    }
+    double g = K->p_g_cin;
+    asm volatile("" : "+v"(g));
+    R.g_cin = g;
+}
+// What stays on the scalar side -- S, the K' group and the closing column differences, 94 doubles -- is fetched ONE GROUP AHEAD of its
+// use: the s_load of group i + 1 is issued before group i's arithmetic, so its latency passes behind 32 f64 instructions instead of in
+// front of an s_waitcnt two instructions later.  The compiler places a scalar load next to its wait, so the loads and their waits are
+// written out.  An asm load is not counted by the compiler: the statement that waits names the loaded registers as "+s", which keeps
+// every reader below it, and as "+v" the last values of the arithmetic that has to stay above it.  Scalar loads return out of order:
+// only lgkmcnt(0) is a valid wait.  Between a load and its wait lies straight-line arithmetic alone (no branch, no call).
+typedef double ow_sd8 __attribute__((ext_vector_type(8)));
+typedef double ow_sd4 __attribute__((ext_vector_type(4)));
+typedef double ow_sd2 __attribute__((ext_vector_type(2)));
+#define OW_KOFF(field) ((int)__builtin_offsetof(OwConsts, field))
+// wait for `cur` (loaded earlier), then issue the load of the next eight doubles into `nxt`; xa, xb: see above
+#define OW_SWAIT_FETCH8D(nxt, off, cur, xa, xb) \
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_load_dwordx16 %0, %4, %5" : "=&s"(nxt), "+s"(cur), "+v"(xa), "+v"(xb) : "s"(K0), "i"(off))
+// one row of S times both right-hand sides (dk_step's sums: they start at 0.0)
+#define OW_S_ROW(i, row) { double sum_a = 0.0, sum_b = 0.0; \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) { const double s = row[j]; sum_a += s * ra[j]; sum_b += s * rb[j]; } \
+    pa[i] = sum_a; pb[i] = sum_b; }
+
+OW_DEV void dk_rhs(const double* __restrict__ an, const DkSt& st, double input, double g_ldr_prev, double p_g_cin, double rhs[8], double& cin_now) {
+    const double* v = st.v;     // an: DkPairRes::an
+    rhs[0] = an[0] * v[0] + an[1] * v[2];
+    rhs[1] = an[2] * v[1] + an[3] * v[7];
+    rhs[2] = an[4] * v[0] + an[5] * v[2] + an[6] * v[5];
+    rhs[3] = an[7] * v[3] + an[8] * v[4];
+    rhs[4] = an[9] * v[3] + an[10] * v[4];
+    rhs[5] = an[11] * v[2] + an[12] * v[5] + an[13] * v[6];
+    rhs[6] = an[14] * v[5] + an[15] * v[6] + an[16] * v[7];
+    rhs[7] = an[17] * v[1] + an[18] * v[6] + an[19] * v[7];
     rhs[7] -= g_ldr_prev * st.v[7];
     cin_now = p_g_cin * input + st.j_cin;
     rhs[0] += cin_now + st.cin_prev;
@@ -738,61 +805,78 @@ OW_DEV void dk_newton_update(double k00, double k01, double k10, double k11, dou
     dk_ic_gm(vn1, ic1, gm1);
 }
 // dk_step's closing updates (:535-552) for one state
-OW_DEV double dk_close(const OwConsts* __restrict__ K, DkSt& st, const double v_pred[8], double sm_k, double cin_now, double input,
+OW_DEV double dk_close(const double sfb_ni[2], const ow_sd8& sni_d1, const ow_sd8& sni_d2, double p_gc_1pc, double p_c_cin,
+                       const double* __restrict__ s_fb_col, DkSt& st, const double v_pred[8], double sm_k, double cin_now, double input,
                        double vn0, double vn1, double ic0, double ic1, double gm0, double gm1) {
-    const double dot = K->p_sfb_ni[0] * ic0 + K->p_sfb_ni[1] * ic1;
+    const double dot = sfb_ni[0] * ic0 + sfb_ni[1] * ic1;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const double s_ni_i = ic0 * K->p_sni_d1[i] + ic1 * K->p_sni_d2[i];
-        st.v[i] = v_pred[i] + s_ni_i - sm_k * dot * K->p_s_fb_col[i];
+        const double s_ni_i = ic0 * sni_d1[i] + ic1 * sni_d2[i];
+        st.v[i] = v_pred[i] + s_ni_i - sm_k * dot * s_fb_col[i];
     }
     st.cin_prev = cin_now;
     const double dv_cin = input - st.v[0];
-    st.j_cin = -K->p_gc_1pc * dv_cin - K->p_c_cin * st.j_cin;
+    st.j_cin = -p_gc_1pc * dv_cin - p_c_cin * st.j_cin;
     st.i_nl[0] = ic0; st.i_nl[1] = ic1;
     st.v_nl[0] = vn0; st.v_nl[1] = vn1;
     st.gm[0] = gm0; st.gm[1] = gm1;
     return st.v[6];
 }
 __device__ inline void dk_step_pair(DkSt& sa, DkSt& sb, double in_a, double in_b, double g_ldr, double g_ldr_prev,
-                                    const OwConsts* __restrict__ K0, double& out_a, double& out_b) {
-    const OwConsts* __restrict__ K = k_reload(K0);
+                                    const OwConsts* __restrict__ K0, const DkPairRes& R, double& out_a, double& out_b) {
+    ow_sd8 s0, s1;
+    // row 0 of S: behind the right-hand sides (every row of A_neg v reads one of the node voltages named here, so none of them moves up)
+    asm volatile("s_load_dwordx16 %0, %9, %10"
+                 : "=s"(s0), "+v"(sa.v[0]), "+v"(sa.v[1]), "+v"(sa.v[3]), "+v"(sa.v[5]), "+v"(sb.v[0]), "+v"(sb.v[1]), "+v"(sb.v[3]), "+v"(sb.v[5])
+                 : "s"(K0), "i"(OW_KOFF(p_s)));
     double ra[8], rb[8], cin_a, cin_b;
-    dk_rhs(K->p_a_neg, sa, in_a, g_ldr_prev, K->p_g_cin, ra, cin_a);
-    dk_rhs(K->p_a_neg, sb, in_b, g_ldr_prev, K->p_g_cin, rb, cin_b);
+    dk_rhs(R.an, sa, in_a, g_ldr_prev, R.g_cin, ra, cin_a);
+    dk_rhs(R.an, sb, in_b, g_ldr_prev, R.g_cin, rb, cin_b);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { ra[i] += K->p_two_w[i]; rb[i] += K->p_two_w[i]; }
+    for (int i = 0; i < 8; ++i) { ra[i] += R.two_w[i]; rb[i] += R.two_w[i]; }
     double pa[8], pb[8];
-    {
-        const OwConsts* __restrict__ Kb = k_reload(K0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            double sum_a = 0.0, sum_b = 0.0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const double s = Kb->p_s[i][j]; sum_a += s * ra[j]; sum_b += s * rb[j]; }
-            pa[i] = sum_a; pb[i] = sum_b;
-        }
-        const OwConsts* __restrict__ Kc = k_reload(K0);
-#pragma unroll
-        for (int i = 4; i < 8; ++i) {
-            double sum_a = 0.0, sum_b = 0.0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const double s = Kc->p_s[i][j]; sum_a += s * ra[j]; sum_b += s * rb[j]; }
-            pa[i] = sum_a; pb[i] = sum_b;
-        }
-    }
-    K = k_reload(K0);
+    OW_SWAIT_FETCH8D(s1, OW_KOFF(p_s) + 1 * 64, s0, ra[7], rb[7]);
+    OW_S_ROW(0, s0)
+    OW_SWAIT_FETCH8D(s0, OW_KOFF(p_s) + 2 * 64, s1, pa[0], pb[0]);
+    OW_S_ROW(1, s1)
+    OW_SWAIT_FETCH8D(s1, OW_KOFF(p_s) + 3 * 64, s0, pa[1], pb[1]);
+    OW_S_ROW(2, s0)
+    OW_SWAIT_FETCH8D(s0, OW_KOFF(p_s) + 4 * 64, s1, pa[2], pb[2]);
+    OW_S_ROW(3, s1)
+    OW_SWAIT_FETCH8D(s1, OW_KOFF(p_s) + 5 * 64, s0, pa[3], pb[3]);
+    OW_S_ROW(4, s0)
+    OW_SWAIT_FETCH8D(s0, OW_KOFF(p_s) + 6 * 64, s1, pa[4], pb[4]);
+    OW_S_ROW(5, s1)
+    OW_SWAIT_FETCH8D(s1, OW_KOFF(p_s) + 7 * 64, s0, pa[5], pb[5]);
+    OW_S_ROW(6, s0)
+    // behind the last row: K' (p_k), and p_s_fb_fb, p_nv_sfb[2], p_sfb_ni[2], which lie one after the other
+    ow_sd4 kk, kf;
+    ow_sd2 kn;
+    static_assert(OW_KOFF(p_nv_sfb) == OW_KOFF(p_s_fb_fb) + 8 && OW_KOFF(p_sfb_ni) == OW_KOFF(p_s_fb_fb) + 24, "OwConsts layout");
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_load_dwordx8 %0, %6, %7\n\ts_load_dwordx8 %1, %6, %8\n\ts_load_dwordx4 %2, %6, %9"
+                 : "=&s"(kk), "=&s"(kf), "=&s"(kn), "+s"(s1), "+v"(pa[6]), "+v"(pb[6])
+                 : "s"(K0), "i"(OW_KOFF(p_k)), "i"(OW_KOFF(p_s_fb_fb)), "i"(OW_KOFF(p_s_fb_fb) + 32));
+    OW_S_ROW(7, s1)
+    // behind the part that depends on g_ldr alone and v_pred: the closing column differences, p_c_cin and p_gc_1pc
+    ow_sd8 d1, d2;
+    ow_sd2 cc;
+    static_assert(OW_KOFF(p_gc_1pc) == OW_KOFF(p_c_cin) + 8, "OwConsts layout");
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_load_dwordx16 %0, %8, %9\n\ts_load_dwordx16 %1, %8, %10\n\ts_load_dwordx4 %2, %8, %11"
+                 : "=&s"(d1), "=&s"(d2), "=&s"(cc), "+s"(kk), "+s"(kf), "+s"(kn), "+v"(pa[7]), "+v"(pb[7])
+                 : "s"(K0), "i"(OW_KOFF(p_sni_d1)), "i"(OW_KOFF(p_sni_d2)), "i"(OW_KOFF(p_c_cin)));
+    const double p_s_fb_fb = kf[0], p_nv_sfb0 = kf[1], p_nv_sfb1 = kf[2], p_sfb_ni0 = kf[3], p_sfb_ni1 = kn[0];
     // the part of the step that depends on g_ldr alone: once per engine
-    const double sm_k = ow_div(g_ldr, 1.0 + K->p_s_fb_fb * g_ldr);
-    const double k00 = K->p_k[0][0] - sm_k * K->p_nv_sfb[0] * K->p_sfb_ni[0];
-    const double k01 = K->p_k[0][1] - sm_k * K->p_nv_sfb[0] * K->p_sfb_ni[1];
-    const double k10 = K->p_k[1][0] - sm_k * K->p_nv_sfb[1] * K->p_sfb_ni[0];
-    const double k11 = K->p_k[1][1] - sm_k * K->p_nv_sfb[1] * K->p_sfb_ni[1];
+    const double sm_k = ow_div(g_ldr, 1.0 + p_s_fb_fb * g_ldr);
+    double k00 = kk[0] - sm_k * p_nv_sfb0 * p_sfb_ni0;      // p_k[0][0], [0][1], [1][0], [1][1]
+    double k01 = kk[1] - sm_k * p_nv_sfb0 * p_sfb_ni1;
+    double k10 = kk[2] - sm_k * p_nv_sfb1 * p_sfb_ni0;
+    double k11 = kk[3] - sm_k * p_nv_sfb1 * p_sfb_ni1;
     const double smv_a = sm_k * pa[7], smv_b = sm_k * pb[7];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { const double c = K->p_s_fb_col[i]; pa[i] = pa[i] - smv_a * c; pb[i] = pb[i] - smv_b * c; }   // v_pred
-    const double p0a = pa[0] - pa[1], p1a = pa[2] - pa[3];
-    const double p0b = pb[0] - pb[1], p1b = pb[2] - pb[3];
+    for (int i = 0; i < 8; ++i) { const double c = R.s_fb_col[i]; pa[i] = pa[i] - smv_a * c; pb[i] = pb[i] - smv_b * c; }   // v_pred
+    double p0a = pa[0] - pa[1], p1a = pa[2] - pa[3];
+    double p0b = pb[0] - pb[1], p1b = pb[2] - pb[3];
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(d1), "+s"(d2), "+s"(cc), "+v"(k11), "+v"(p1a), "+v"(p1b), "+v"(pa[7]), "+v"(pb[7]));
     double vn0a = sa.v_nl[0], vn1a = sa.v_nl[1], ic0a = sa.i_nl[0], ic1a = sa.i_nl[1], gm0a = sa.gm[0], gm1a = sa.gm[1];
     double vn0b = sb.v_nl[0], vn1b = sb.v_nl[1], ic0b = sb.i_nl[0], ic1b = sb.i_nl[1], gm0b = sb.gm[0], gm1b = sb.gm[1];
     bool done_a = false, done_b = false;
@@ -809,10 +893,12 @@ __device__ inline void dk_step_pair(DkSt& sa, DkSt& sb, double in_a, double in_b
         dk_newton_update(k00, k01, k10, k11, f0a, f1a, done_a, vn0a, vn1a, ic0a, ic1a, gm0a, gm1a);
         dk_newton_update(k00, k01, k10, k11, f0b, f1b, done_b, vn0b, vn1b, ic0b, ic1b, gm0b, gm1b);
     }
-    K = k_reload(K0);
-    out_a = dk_close(K, sa, pa, sm_k, cin_a, in_a, vn0a, vn1a, ic0a, ic1a, gm0a, gm1a);
-    out_b = dk_close(K, sb, pb, sm_k, cin_b, in_b, vn0b, vn1b, ic0b, ic1b, gm0b, gm1b);
+    const double sfb_ni[2] = {p_sfb_ni0, p_sfb_ni1};
+    out_a = dk_close(sfb_ni, d1, d2, cc[1], cc[0], R.s_fb_col, sa, pa, sm_k, cin_a, in_a, vn0a, vn1a, ic0a, ic1a, gm0a, gm1a);
+    out_b = dk_close(sfb_ni, d1, d2, cc[1], cc[0], R.s_fb_col, sb, pb, sm_k, cin_b, in_b, vn0b, vn1b, ic0b, ic1b, gm0b, gm1b);
 }
+#undef OW_S_ROW
+#undef OW_SWAIT_FETCH8D
 
 // DkPreamp::reset -> full_dc_solve at the current R_ldr (dk_preamp_legacy.rs:369-412,628-640).
 // Rare path (engine reset, NaN guards); dynamic indexing is fine here.
@@ -923,7 +1009,7 @@ __device__ inline double power_amp(double input) {
         const double v = A * error;
         const double v_sq = v * v;
         const double vt_sq = 0.013 * 0.013;
-        const double exp_term = exp(OW_DIV_C(-v_sq, 0.013 * 0.013));
+        const double exp_term = exp_any(OW_DIV_C(-v_sq, 0.013 * 0.013));
         const double q = 0.1;
         const double cross_gain = q + (1.0 - q) * (1.0 - exp_term);
         const double v_cross = v * cross_gain;

@@ -37,8 +37,10 @@ __global__ __launch_bounds__(64) void k_debug_dk_step(const OwConsts* __restrict
         DkSt sm, ss;
         dk_load(sm, cs_in, n, a, 0);
         dk_load(ss, cs_in, n, b, 0);
+        DkPairRes R;
+        dk_pair_res_load(R, K);
         double om, os;
-        dk_step_pair(sm, ss, input[a], input[b], g_ldr[a], g_ldr_prev[a], K, om, os);
+        dk_step_pair(sm, ss, input[a], input[b], g_ldr[a], g_ldr_prev[a], K, R, om, os);
         if (va) { dk_store(sm, cs_out, n, a, 0); out[a] = om; }
         if (vb) { dk_store(ss, cs_out, n, b, 0); out[b] = os; }
     } else if constexpr (FORM == DKF_WIDE) {

@@ -1351,6 +1351,8 @@ void k_preamp_pair(const OwConsts* __restrict__ K, double* __restrict__ cs, cons
             for (int i = 0; i < 3; ++i) { ua[i] = 0.0; ub[i] = 0.0; }
         }
     }
+    DkPairRes R;      // A_neg's non-zeros, 2w and S's feedback column: resident in vector registers for the whole block
+    dk_pair_res_load(R, K);
     uint32_t nan_resets = 0;
     double sh_depth = __longlong_as_double(0x7FF8000000000000LL), sh_top = 0.0, sh_lower = 0.0;      // as k_preamp
     // staging flags of engine row `lane` (see k_preamp); broadcast per row with v_readlane: lanes 0-31 stage row r, lanes 32-63 row r + 32
@@ -1403,12 +1405,12 @@ void k_preamp_pair(const OwConsts* __restrict__ K, double* __restrict__ cs, cons
             }
             for (int j = 0; j < osr; ++j) {
                 const size_t idx = (size_t)((base + n) * osr + j);
-                const double branch = 680.0 + rc[j];
+                const double branch = 680.0 + (j ? rc[1] : rc[0]);      // (selects, not indexed arrays: these stay in registers)
                 const double low = sh_lower > 0.0 ? ow_div(sh_lower * branch, sh_lower + branch) : 0.0;
                 const double r_new = fmax(sh_top + low, 1000.0);               // tremolo.rs:152-167; set_ldr_resistance, :620-626
                 if (fabs(r_new - r_ldr) > 0.01) { r_ldr = r_new; g_ldr = ow_div(1.0, r_new); }
                 double om, os;
-                dk_step_pair(sm, ss, in[j], 0.0, g_ldr, g_prev, K, om, os);     // shadow input 0.0 (dk_preamp_legacy.rs:599)
+                dk_step_pair(sm, ss, j ? in[1] : in[0], 0.0, g_ldr, g_prev, K, R, om, os);    // shadow input 0.0 (dk_preamp_legacy.rs:599)
                 g_prev = g_ldr;                                                   // :604
                 double result = om - os;                                          // main - pump, :608
                 if (!isfinite(result)) {                                          // :610-615

@@ -543,6 +543,23 @@ __device__ __noinline__ __attribute__((const)) double noise_fade_env(double t) {
 // and lane.  The reference calls libm tanh, itself good to 1-2 ulp; this one is tanh(x) = z / (z + 2), z = expm1(2|x|) from the
 // same ln 2 reduction as exp_bounded and a degree-13 series: ~45 instructions, <= 2 ulp (measured on the device against an 80-bit
 // reference over the whole domain, tests/test_gpu_division.py::test_tanh_fast_accuracy; glibc's own tanh measures 1.2 there).  OW_LIB_TANH restores the library call.
+// fma3: fma(a, b, c) as ONE three-address v_fma_f64.  A Horner step `p = fma(r, p, coeff)` whose coefficient lives in a register across
+// a loop is otherwise selected as the two-address v_fmac_f64, which accumulates into its addend: the coefficient is copied first
+// (v_mov_b64 + v_fmac_f64, in the power amp's Newton loop before every step of both polynomials).  The same fused operation on the same
+// operands: the same bits.  OW_FMA3=0 restores __builtin_fma.  (noconvergent: device code takes an asm statement for a cross-lane
+// operation unless told otherwise, and a loop with one in it -- or with a call of a function that holds one -- is no longer unrolled.)
+#ifndef OW_FMA3
+#define OW_FMA3 1
+#endif
+OW_DEV double fma3(double a, double b, double c) {
+#if OW_FMA3
+    double d;
+    [[clang::noconvergent]] { asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); }
+    return d;
+#else
+    return __builtin_fma(a, b, c);
+#endif
+}
 OW_DEV double tanh_fast(double x) {
 #ifdef OW_LIB_TANH
     return tanh(x);
@@ -554,17 +571,17 @@ OW_DEV double tanh_fast(double x) {
     double r = __builtin_fma(__longlong_as_double((long long)0xbfe62e42fefa39efULL), n, y);
     r = __builtin_fma(__longlong_as_double((long long)0xbc7abc9e3b39803fULL), n, r);
     double q = 1.0 / 6227020800.0;                     // 1/13!
-    q = __builtin_fma(q, r, 1.0 / 479001600.0);
-    q = __builtin_fma(q, r, 1.0 / 39916800.0);
-    q = __builtin_fma(q, r, 1.0 / 3628800.0);
-    q = __builtin_fma(q, r, 1.0 / 362880.0);
-    q = __builtin_fma(q, r, 1.0 / 40320.0);
-    q = __builtin_fma(q, r, 1.0 / 5040.0);
-    q = __builtin_fma(q, r, 1.0 / 720.0);
-    q = __builtin_fma(q, r, 1.0 / 120.0);
-    q = __builtin_fma(q, r, 1.0 / 24.0);
-    q = __builtin_fma(q, r, 1.0 / 6.0);
-    q = __builtin_fma(q, r, 0.5);
+    q = fma3(q, r, 1.0 / 479001600.0);
+    q = fma3(q, r, 1.0 / 39916800.0);
+    q = fma3(q, r, 1.0 / 3628800.0);
+    q = fma3(q, r, 1.0 / 362880.0);
+    q = fma3(q, r, 1.0 / 40320.0);
+    q = fma3(q, r, 1.0 / 5040.0);
+    q = fma3(q, r, 1.0 / 720.0);
+    q = fma3(q, r, 1.0 / 120.0);
+    q = fma3(q, r, 1.0 / 24.0);
+    q = fma3(q, r, 1.0 / 6.0);
+    q = fma3(q, r, 0.5);
     const double em1 = __builtin_fma(r * r, q, r);     // expm1(r), |r| <= ln2 / 2
     const double s = __longlong_as_double((long long)(1023 + (int)n) << 52);   // 2^n, 0 <= n <= 58
     const double z = __builtin_fma(s, em1, s - 1.0);   // expm1(2|x|) = 2^n expm1(r) + (2^n - 1)
