@@ -628,6 +628,42 @@ typedef struct ow_overshoot_row {
 long long ow_overshoot(const ow_note_job* jobs, size_t n_jobs, const ow_overshoot_cfg* cfg, ow_overshoot_row* rows_out, double* audio_out,
                        size_t audio_stride);
 
+/* ---- bark audit (`preamp-bench bark-audit`, tools/preamp-bench/src/main.rs:551-664) --------------------------------------------------
+ * Per (note, velocity): how much second harmonic the reed carries into the pickup and out of the preamp.  Stage 1: ModalReed::new with
+ * onset 0 (no MLP, no attack noise, no onset ramp), seed note * 2654435761; stage 2: Pickup::new_with_scale(44100, the table's
+ * displacement scale); stage 3: a fresh preamp of preamp_kind at a static 1 Mohm, per-sample 2x oversampling (process_oversampled).
+ * The figures are taken over the samples [window_start, window_end) = [(measure_start_s * 44100) as usize, (duration_s * 44100) as usize). */
+typedef struct ow_bark_cfg {
+    uint32_t struct_size;  /* = sizeof(ow_bark_cfg) of the caller's header */
+    uint32_t job_size;     /* = sizeof(ow_note_job) of the caller's header (the stride of `jobs`) */
+    double duration_s;     /* the command's constant 0.5 (:565), a parameter here */
+    double measure_start_s; /* the command's constant 0.25 (:566) */
+    int device;
+    int preamp_kind;       /* create_preamp: OW_PREAMP_LEGACY8 or OW_PREAMP_MELANGE12 */
+} ow_bark_cfg;
+typedef struct ow_bark_row {
+    uint8_t note, velocity;
+    uint8_t reserved[6];
+    uint32_t window_start, window_end;
+    double fundamental_hz;                    /* params.fundamental_hz (undetuned): H1 is analysed there, H2 at 2.0 * fundamental_hz */
+    double displacement_scale;                /* tables::pickup_displacement_scale(note), the value the pickup ran with */
+    double reed_peak, y_peak;                 /* max |reed| over the window; reed_peak * displacement_scale */
+    double pu_peak;                           /* max |pickup| over the window (volts; the command prints mV) */
+    double pu_h1, pu_h2, pu_h2_h1;            /* dft_magnitude (:893-903) of the pickup window, phase counted from window_start; h2 / h1, 0.0 unless h1 > 1e-15 */
+    double pre_h1, pre_h2, pre_h2_h1;         /* the same of the preamp window */
+} ow_bark_row;
+/* cmd_bark_audit for n_jobs (note, velocity) jobs at once.  rows_out: [n_jobs].  taps_out: NULL, or host f64 [n_jobs][3][tap_stride >=
+ * samples] receiving the reed, pickup and preamp rows; asking for them changes no number.  The rows stay in HBM between the stages;
+ * large grids run in chunks of a fixed device-memory budget (OW_BARK_CHUNK=<jobs> caps a chunk; tests use it).  A job's numbers do not
+ * depend on the other jobs of the call or on the chunking.  The legacy preamp runs as a row of sixteen lanes per solver state for
+ * launches of up to 4 096 jobs and as a lane pair above (OW_BARK_ROW=0/1 forces the form; the two give the same bits).  n_jobs == 0
+ * returns the sample count and touches nothing; a duration of 0 samples needs no device (every figure 0).
+ * Returns the samples per job, <0 on error.  Refused before any device work (ow_last_error says why): "ABI mismatch", null arguments, a
+ * note outside 33..96, a velocity above 127, an unknown preamp_kind, a duration or start that is negative or not finite, a duration giving
+ * 2^31 samples or more, a start that leaves no sample to measure, a short tap_stride. */
+long long ow_bark_audit(const ow_note_job* jobs, size_t n_jobs, const ow_bark_cfg* cfg, ow_bark_row* rows_out, double* taps_out,
+                        size_t tap_stride);
+
 /* ---- the pump measurements: `preamp-bench pump-sweep` / `pump-trace` / `pump-spike` / `pump-step` / `pump-sinusoid` (main.rs:2329-3063) ----
  * These commands drive gen_preamp::process_sample directly on a CircuitState::default() of the melange 12-node preamp: no adapter, no
  * settled state, no main - shadow difference, no thermal noise.  One point is one run of one such state. */

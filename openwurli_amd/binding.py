@@ -224,6 +224,23 @@ class OwOvershootRow(C.Structure):
     _fields_ = [("note", C.c_uint8), ("velocity", C.c_uint8), ("reserved", C.c_uint8 * 6)] + [(f, C.c_double) for f in OVERSHOOT_ROW_FIELDS]
 
 
+class OwBarkCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("job_size", C.c_uint32), ("duration_s", C.c_double), ("measure_start_s", C.c_double),
+                ("device", C.c_int), ("preamp_kind", C.c_int)]
+
+    def __init__(self, duration_s=0.5, measure_start_s=0.25, device=0, preamp_kind=0):
+        super().__init__(C.sizeof(OwBarkCfg), C.sizeof(OwNoteJob), duration_s, measure_start_s, device, preamp_kind)
+
+
+BARK_ROW_FIELDS = ("fundamental_hz", "displacement_scale", "reed_peak", "y_peak", "pu_peak", "pu_h1", "pu_h2", "pu_h2_h1", "pre_h1", "pre_h2",
+                   "pre_h2_h1")
+
+
+class OwBarkRow(C.Structure):
+    _fields_ = [("note", C.c_uint8), ("velocity", C.c_uint8), ("reserved", C.c_uint8 * 6), ("window_start", C.c_uint32),
+                ("window_end", C.c_uint32)] + [(f, C.c_double) for f in BARK_ROW_FIELDS]
+
+
 PUMP_STATIC, PUMP_STEP, PUMP_RAMP, PUMP_LOGCOS = 0, 1, 2, 3                     # include/openwurli_hip.h OW_PUMP_*
 
 
@@ -335,6 +352,7 @@ SYMBOLS = {
     "ow_intermod_probes": (C.c_int, [C.c_uint8, _VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "ow_intermod_audit": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwIntermodCfg), _VP, _VP, C.c_size_t]),
     "ow_overshoot": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwOvershootCfg), _VP, _VP, C.c_size_t]),
+    "ow_bark_audit": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwBarkCfg), _VP, _VP, C.c_size_t]),
     "ow_pump_measure": (C.c_int, [_VP, C.c_size_t, C.POINTER(OwPumpCfg), _VP, _VP, C.c_size_t]),
 }
 

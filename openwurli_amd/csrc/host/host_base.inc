@@ -245,7 +245,9 @@ static bool switch_from_set(SwitchKind kind, long long lo, long long hi, long lo
     X(int, chain_wide, -1, "OW_CHAIN_WIDE", SW_TRI, -1, 1, false)                      /* job paths (host_jobs_chain.inc): a quad of lanes per preamp state never / always; -1: up to 8 192 jobs */ \
     X(int, job_fused, -1, "OW_JOB_FUSED", SW_TRI, -1, 1, false)                        /* ... as preamp | output stage on two wavefronts (k_job_chain_fused) never / always; -1: up to 4 096 jobs */ \
     X(bool, job_overlap, true, "OW_JOB_OVERLAP", SW_BOOL, 0, 1, false)                 /* 0: the batch render's voices in front of the fused chain instead of beside it */ \
-    X(int, job_row, -1, "OW_JOB_ROW", SW_TRI, -1, 1, false)                            /* ... with a row of sixteen lanes per solver state (k_job_chain_row) never / always; -1: up to 1 024 jobs */
+    X(int, job_row, -1, "OW_JOB_ROW", SW_TRI, -1, 1, false)                            /* ... with a row of sixteen lanes per solver state (k_job_chain_row) never / always; -1: up to 1 024 jobs */ \
+    X(long long, bark_chunk, 0, "OW_BARK_CHUNK", SW_COUNT, 1, LLONG_MAX, false)        /* at most n jobs per chunk of ow_bark_audit (tests); 0: the device-memory budget alone */ \
+    X(int, bark_row, -1, "OW_BARK_ROW", SW_TRI, -1, 1, false)                          /* force the lane-pair / row chain kernel of ow_bark_audit (legacy); -1: launches of up to 4 096 jobs take the row */
 struct Switches {
 #define X(type, name, dflt, env, kind, lo, hi, settable) type name = dflt;
     OW_SWITCH_TABLE(X)

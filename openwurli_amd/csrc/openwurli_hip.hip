@@ -43,6 +43,7 @@
 #include "ow_poly_kernels.h"
 #include "ow_centroid_kernels.h"
 #include "ow_note_audit_kernels.h"
+#include "ow_bark_kernels.h"
 #include "ow_pump_kernels.h"
 #include "ow_midi_kernels.h"
 #include "ow_chain_wide.h"
@@ -75,4 +76,5 @@ using owdev::OwEngineOut;
 #include "host/api_render_poly.inc"     // C-ABI: `preamp-bench render-poly` (chord intermodulation, many chords per call)
 #include "host/api_centroid.inc"        // C-ABI: `preamp-bench centroid-track` (spectral centroid over time, many notes per call)
 #include "host/api_note_audit.inc"      // C-ABI: `preamp-bench intermod-audit` / `overshoot` (the note audits, many notes per call)
+#include "host/api_bark_audit.inc"      // C-ABI: `preamp-bench bark-audit` (H2 / H1 per chain stage, many notes per call)
 #include "host/api_pump.inc"            // C-ABI: `preamp-bench pump-sweep` / `pump-trace` / `pump-spike` / `pump-step` / `pump-sinusoid` (the pump measurements)
