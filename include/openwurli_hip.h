@@ -228,6 +228,35 @@ double ow_normalize_scale(const double* samples, size_t n);
  * If out_is_device != 0, `out` is a device pointer and nothing is copied to the host.  Returns samples per job, <0 on error. */
 long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg* cfg, double* out, size_t stride, int out_is_device);
 
+/* ---- note-on MLP corrections given at run time (ml/: train -> model_weights.json -> render, without a rebuild) ---------------------
+ * The reference bakes the network into mlp_weights.rs at compile time; here a weight set, or the corrections themselves, are data of a
+ * batch render.  Nothing else of a job changes: every other ow_job field and ow_batch_cfg mean what they mean to ow_batch_render. */
+#define OW_MLP_HIDDEN 16
+#define OW_MLP_OUTPUTS 11
+typedef struct ow_mlp_weights {            /* mlp_weights.rs, same shapes and order */
+    double w1[16][2], b1[16], w2[16][16], b2[16], w3[11][16], b3[11], target_means[11], target_stds[11];
+} ow_mlp_weights;
+typedef struct ow_mlp_corrections {        /* MlpCorrections, mlp_correction.rs:38-45 */
+    double freq_offsets_cents[5], decay_offsets[5], ds_correction;
+} ow_mlp_corrections;
+/* The built-in set (the one the library's note-ons use).  Host only, no device touched.  Returns 0, <0 on a null pointer. */
+int ow_mlp_default_weights(ow_mlp_weights* out);
+/* MlpCorrections::infer (mlp_correction.rs:61-140) of every (set, point) on the device: out[set * n_points + point]; raw_out (NULL or
+ * [n_sets][n_points][11]) receives the denormalised network outputs before the fade outside MIDI 65..97 and the clamps.
+ * sets == NULL with n_sets == 1 means the built-in set.  velocities are the normalised ones (clamped to 0..1 like the reference's).
+ * Returns 0, <0 on error (a null pointer, a non-finite weight or velocity: refused on the host before the device is touched). */
+int ow_mlp_infer(const ow_mlp_weights* sets, size_t n_sets, const uint8_t* notes, const double* velocities, size_t n_points,
+                 int device, ow_mlp_corrections* out, double* raw_out);
+/* ow_batch_render with job j's note-on taking corr[j] in place of what infer would return; jobs[j].mlp is ignored.  A non-finite
+ * correction or a decay_offsets entry <= 0 (note-on divides by it) is refused on the host: <0, ow_last_error() names job and field. */
+long long ow_batch_render_corrected(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg* cfg, const ow_mlp_corrections* corr,
+                                    double* out, size_t stride, int out_is_device);
+/* ow_batch_render with the network's weights per job: a job with mlp != 0 takes the corrections of sets[set_of_job[j]] at
+ * (note, velocity / 127), a job with mlp == 0 the identity.  ow_mlp_infer into a device table, then the render of
+ * ow_batch_render_corrected; nothing passes through the host in between.  set_of_job[j] >= n_sets or a non-finite weight is refused. */
+long long ow_batch_render_mlp(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg* cfg, const ow_mlp_weights* sets, size_t n_sets,
+                              const uint32_t* set_of_job, double* out, size_t stride, int out_is_device);
+
 /* Plain device buffers for chaining the offline entry points without a host round trip (out_is_device / audio_is_device). */
 void* ow_device_alloc(size_t bytes, int device);   /* NULL on failure */
 void ow_device_free(void* ptr, int device);

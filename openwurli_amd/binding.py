@@ -31,6 +31,19 @@ class OwJob(C.Structure):
                 ("tremolo_depth", C.c_double), ("displacement_scale", C.c_double)]
 
 
+MLP_HIDDEN, MLP_OUTPUTS = 16, 11      # include/openwurli_hip.h OW_MLP_HIDDEN / OW_MLP_OUTPUTS
+
+
+class OwMlpWeights(C.Structure):
+    """mlp_weights.rs, same shapes and order."""
+    _fields_ = [("w1", C.c_double * 2 * 16), ("b1", C.c_double * 16), ("w2", C.c_double * 16 * 16), ("b2", C.c_double * 16),
+                ("w3", C.c_double * 16 * 11), ("b3", C.c_double * 11), ("target_means", C.c_double * 11), ("target_stds", C.c_double * 11)]
+
+
+class OwMlpCorrections(C.Structure):
+    _fields_ = [("freq_offsets_cents", C.c_double * 5), ("decay_offsets", C.c_double * 5), ("ds_correction", C.c_double)]
+
+
 class OwMidiEvent(C.Structure):
     _fields_ = [("engine", C.c_uint32), ("type", C.c_uint8), ("note", C.c_uint8), ("reserved", C.c_uint16), ("value", C.c_float)]
 
@@ -329,6 +342,10 @@ SYMBOLS = {
     "ow_render_note_with_scale": (C.c_longlong, [C.c_uint8, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _VP, C.c_size_t]),
     "ow_normalize_scale": (C.c_double, [_VP, C.c_size_t]),
     "ow_batch_render": (C.c_longlong, [C.POINTER(OwJob), C.c_size_t, C.POINTER(OwBatchCfg), _VP, C.c_size_t, C.c_int]),
+    "ow_mlp_default_weights": (C.c_int, [_VP]),
+    "ow_mlp_infer": (C.c_int, [_VP, C.c_size_t, _VP, _VP, C.c_size_t, C.c_int, _VP, _VP]),
+    "ow_batch_render_corrected": (C.c_longlong, [C.POINTER(OwJob), C.c_size_t, C.POINTER(OwBatchCfg), _VP, _VP, C.c_size_t, C.c_int]),
+    "ow_batch_render_mlp": (C.c_longlong, [C.POINTER(OwJob), C.c_size_t, C.POINTER(OwBatchCfg), _VP, C.c_size_t, _VP, _VP, C.c_size_t, C.c_int]),
     "ow_device_alloc": (_VP, [C.c_size_t, C.c_int]),
     "ow_device_free": (None, [_VP, C.c_int]),
     "ow_host_alloc": (_VP, [C.c_size_t, C.c_int]),

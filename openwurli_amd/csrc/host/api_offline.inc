@@ -49,7 +49,12 @@ static long long render_note_impl(uint8_t midi, double velocity, double dur_s, d
     } catch (const std::exception& ex) { set_err(std::string("ow_render_note: ") + ex.what()); return -1; }
 }
 
-long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg* cfg, double* out, size_t stride, int out_is_device) {
+// The batch render behind ow_batch_render and its two siblings with corrections given at run time (api_mlp.inc).  fill_corr empty:
+// every job's note-on infers its own corrections from the built-in constants (ow_batch_render, the launches it always made).
+// Otherwise the voices read job j's corrections from a device table of n_jobs entries, which fill_corr fills on the call's stream.
+using FillCorr = std::function<void(OfflineCall&, owdev::MlpOut*)>;
+static long long batch_render_impl(const char* who, const ow_job* jobs, size_t n_jobs, const ow_batch_cfg* cfg, double* out, size_t stride, int out_is_device,
+                                   const FillCorr& fill_corr) {
     try {
         if (!jobs || !cfg || !out || n_jobs == 0) throw std::runtime_error("null argument");
         if (cfg->struct_size != sizeof(ow_batch_cfg) || cfg->job_size != sizeof(ow_job)) throw std::runtime_error(abi_mismatch("ow_batch_cfg.struct_size / job_size do"));
@@ -77,6 +82,13 @@ long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg*
         owdev::OwJobDev* d_jobs = m_jobs.as<owdev::OwJobDev>(); double* d_reed = m_reed.as<double>();
         double* d_out = out_is_device ? out : m_out.as<double>();
         HIP_OK(hipMemcpyAsync(d_jobs, hj.data(), sizeof(owdev::OwJobDev) * n_jobs, hipMemcpyHostToDevice, st));
+        DevMem m_corr;
+        const owdev::MlpOut* d_corr = nullptr;
+        if (fill_corr) {
+            m_corr.alloc(sizeof(owdev::MlpOut) * n_jobs);
+            fill_corr(call, m_corr.as<owdev::MlpOut>());
+            d_corr = m_corr.as<owdev::MlpOut>();
+        }
         const JobChainCfg cc{cfg->sample_rate, cfg->device, cfg->preamp_kind, cfg->power_amp_kind, cfg->no_rail_sag};
         // Voices and chain side by side when the chain is the plain legacy one and leaves room on the chip: a job's run time is serial
         // latency in both kernels, so the 13 % the voices take are hidden behind the chain instead of in front of it.
@@ -92,11 +104,11 @@ long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg*
             so2.create(); ev_ready.create(); ev_voice.create();
             HIP_OK(hipEventRecord(ev_ready, st));
             HIP_OK(hipStreamWaitEvent(so2.s, ev_ready, 0));
-            owdev::k_job_voice<<<dim3((unsigned)vblocks), dim3(64), 0, so2.s>>>(dK, d_nt, d_vrec, d_jobs, d_reed, (int)n_jobs, (long long)n, (long long)stride, d_prog);
+            owdev::k_job_voice<<<dim3((unsigned)vblocks), dim3(64), 0, so2.s>>>(dK, d_nt, d_vrec, d_jobs, d_reed, (int)n_jobs, (long long)n, (long long)stride, d_prog, d_corr);
             HIP_OK(hipGetLastError());
             HIP_OK(hipEventRecord(ev_voice, so2.s));
         } else {
-            owdev::k_job_voice<<<dim3((unsigned)vblocks), dim3(64), 0, st>>>(dK, d_nt, d_vrec, d_jobs, d_reed, (int)n_jobs, (long long)n, (long long)stride);
+            owdev::k_job_voice<<<dim3((unsigned)vblocks), dim3(64), 0, st>>>(dK, d_nt, d_vrec, d_jobs, d_reed, (int)n_jobs, (long long)n, (long long)stride, nullptr, d_corr);
             HIP_OK(hipGetLastError());
         }
         run_job_chain(call, cc, hj, d_jobs, d_reed, d_out, n_jobs, (long long)n, (long long)stride, d_prog);
@@ -110,7 +122,10 @@ long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg*
         if (!out_is_device) HIP_OK(hipMemcpyAsync(out, d_out, sizeof(double) * n_jobs * stride, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         return (long long)n;
-    } catch (const std::exception& ex) { set_err(std::string("ow_batch_render: ") + ex.what()); return -1; }
+    } catch (const std::exception& ex) { set_err(std::string(who) + ": " + ex.what()); return -1; }
+}
+long long ow_batch_render(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg* cfg, double* out, size_t stride, int out_is_device) {
+    return batch_render_impl("ow_batch_render", jobs, n_jobs, cfg, out, stride, out_is_device, FillCorr());
 }
 
 void* ow_device_alloc(size_t bytes, int device) {

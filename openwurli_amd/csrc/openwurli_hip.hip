@@ -50,6 +50,7 @@
 #include "ow_chain_stream.h"
 #include "ow_vm_kernels.h"
 #include <condition_variable>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -69,6 +70,7 @@ using owdev::OwEngineOut;
 #include "host/api_engines.inc"         // C-ABI: the WurliEngine API (engine.rs)
 #include "host/api_test_hooks.inc"      // C-ABI of include/openwurli_hip_test.h: host-logic hooks, diagnostics, switches
 #include "host/api_offline.inc"         // C-ABI: render_note, batch render, WAV writers, feature stage
+#include "host/api_mlp.inc"             // C-ABI: note-on MLP corrections given at run time (weight sets per job, explicit corrections)
 #include "host/api_alias_audit.inc"     // C-ABI: the click-band alias audit (alias_audit.rs)
 #include "host/api_midi_render.inc"     // C-ABI: `preamp-bench render-midi` (SMF reader, voice manager, chain)
 #include "host/api_calibrate.inc"       // C-ABI: `preamp-bench calibrate` / `sensitivity` (the calibration sweep)

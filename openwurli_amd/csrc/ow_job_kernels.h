@@ -26,9 +26,10 @@ struct OwJobDev {           // device copy of ow_job
 enum { JOB_OUT_FINAL = 0, JOB_OUT_PA_INPUT = 1 };
 
 // Voice::note_on + Voice::render for n samples, lane = job.  reed[job][n] (row stride `stride`).
+// corr != nullptr: job j's note-on takes corr[j] in place of what MlpCorrections::infer would return (jobs[j].mlp is not looked at).
 __global__ __launch_bounds__(64) void k_job_voice(const OwConsts* __restrict__ K, const double* __restrict__ nt, double* __restrict__ vrec,
                                                   const OwJobDev* __restrict__ jobs, double* __restrict__ reed, int n_jobs, long long n,
-                                                  long long stride, int* __restrict__ prog = nullptr) {
+                                                  long long stride, int* __restrict__ prog = nullptr, const MlpOut* __restrict__ corr = nullptr) {
     __shared__ double tile[64 * (OW_VCHUNK + 1)];
     const int lane = threadIdx.x;
     const int jb = blockIdx.x * 64;
@@ -41,10 +42,15 @@ __global__ __launch_bounds__(64) void k_job_voice(const OwConsts* __restrict__ K
         const OwJobDev jd = jobs[j];
         const int note = jd.note < OW_MIDI_LO ? OW_MIDI_LO : (jd.note > OW_MIDI_HI ? OW_MIDI_HI : jd.note);
         const double vel = (double)jd.velocity / 127.0;                    // main.rs:403
-        double raw[11];
-        mlp_raw_scalar(clampd(((double)note - 21.0) / (108.0 - 21.0), 0.0, 1.0), clampd(vel, 0.0, 1.0), raw);
-        const MlpOut corr = mlp_finish(note, raw, jd.mlp != 0);
-        note_on_lane(rec, nt, K, note, vel, (uint32_t)jd.note * 2654435761u, corr);   // main.rs:404-405
+        if (corr) {                                                        // wave-uniform: the job's corrections are given (ow_batch_render_corrected / _mlp)
+            const MlpOut given = corr[j];
+            note_on_lane(rec, nt, K, note, vel, (uint32_t)jd.note * 2654435761u, given);
+        } else {
+            double raw[11];
+            mlp_raw_scalar(clampd(((double)note - 21.0) / (108.0 - 21.0), 0.0, 1.0), clampd(vel, 0.0, 1.0), raw);
+            const MlpOut inferred = mlp_finish(note, raw, jd.mlp != 0);
+            note_on_lane(rec, nt, K, note, vel, (uint32_t)jd.note * 2654435761u, inferred);   // main.rs:404-405
+        }
         if (jd.has_ds) rec[VF_DS * 64] = jd.displacement_scale;                        // --displacement-scale (pickup.rs:114-116)
         if (jd.no_attack_noise) rec[VF_NCNT * 64] = bitsd(dbits(rec[VF_NCNT * 64]) & 0xFFFFFFFF00000000ull);   // --no-attack-noise: remaining = 0 (hammer.rs:187-189)
         v.load(rec);

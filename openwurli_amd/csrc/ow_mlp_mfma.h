@@ -68,6 +68,59 @@ __device__ inline void mlp_raw_mfma(double* __restrict__ h, double in0, double i
     __syncthreads();
 }
 
+// One weight set in device memory, laid out as ow_mlp_weights (include/openwurli_hip.h; mlp_weights.rs' shapes and order).
+struct MlpWeightsDev {
+    double w1[16][2], b1[16], w2[16][16], b2[16], w3[11][16], b3[11], target_means[11], target_stds[11];
+};
+
+// The same forward pass with the weights of a set given at run time (read from device memory, not from the built-in constants).
+// Layer 1 in the reference's scalar order, layers 2 and 3 on the matrix cores with the set's weights as the A operand.
+__device__ inline void mlp_raw_mfma(double* __restrict__ h, const MlpWeightsDev* __restrict__ w, double in0, double in1, double raw[11]) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        double sum = w->b1[i];
+        sum += w->w1[i][0] * in0;
+        sum += w->w1[i][1] * in1;
+        h[lane * 17 + i] = sum > 0.0 ? sum : 0.0;
+    }
+    __syncthreads();
+    mlp_layer_mfma(h, w->w2, w->b2, 16, true);
+    mlp_layer_mfma(h, w->w3, w->b3, 11, false);
+#pragma unroll
+    for (int i = 0; i < 11; ++i) raw[i] = h[lane * 17 + i] * w->target_stds[i] + w->target_means[i];
+    __syncthreads();
+}
+
+// MlpCorrections::infer (mlp_correction.rs:61-140) for many (weight set, point) pairs: block (x, y) = 64 points of set y, so a
+// wavefront's MFMA A operand is ONE set's weights and blocks never mix sets.
+//   set_begin == nullptr: every set evaluates the same n_points points; out[set * n_points + p] (raw_out likewise, or nullptr).
+//   set_begin != nullptr: the points are packed set by set, set y owns [set_begin[y], set_begin[y + 1]); point q writes
+//                         out[scatter[q]] (the batch render: q = a job of that set, scatter[q] = its index).  No raw_out.
+// enabled: nullptr (all on) or one byte per point; 0 gives the identity, as `mlp` off does at note-on.
+__global__ __launch_bounds__(64) void k_mlp_infer(const MlpWeightsDev* __restrict__ sets, const uint8_t* __restrict__ notes, const double* __restrict__ vels,
+                                                  const uint8_t* __restrict__ enabled, unsigned n_points, const uint32_t* __restrict__ set_begin,
+                                                  const uint32_t* __restrict__ scatter, MlpOut* __restrict__ out, double* __restrict__ raw_out) {
+    __shared__ double h[64 * 17];
+    const unsigned set = blockIdx.y;
+    const unsigned lo = set_begin ? set_begin[set] : 0u, hi = set_begin ? set_begin[set + 1] : n_points;
+    const unsigned first = lo + blockIdx.x * 64u;
+    if (first >= hi) return;                               // block-uniform, ahead of every barrier
+    const unsigned p = first + threadIdx.x;
+    const bool valid = p < hi;
+    const int note = valid ? (int)notes[p] : 60;
+    const double vel = valid ? vels[p] : 0.0;
+    const double in0 = clampd(((double)note - 21.0) / (108.0 - 21.0), 0.0, 1.0), in1 = clampd(vel, 0.0, 1.0);
+    double raw[11];
+    mlp_raw_mfma(h, sets + set, in0, in1, raw);
+    if (!valid) return;
+    const MlpOut o = mlp_finish(note, raw, enabled ? enabled[p] != 0 : true);
+    const size_t at = set_begin ? (size_t)scatter[p] : (size_t)set * n_points + p;
+    out[at] = o;
+    if (raw_out)
+        for (int i = 0; i < 11; ++i) raw_out[at * 11 + i] = raw[i];
+}
+
 // debug/test kernel: raw MLP outputs for n (note, velocity) pairs, scalar or MFMA path
 __global__ __launch_bounds__(64) void k_debug_mlp(const uint8_t* __restrict__ notes, const double* __restrict__ vels, int n, double* __restrict__ out, int use_mfma) {
     __shared__ double h[64 * 17];
