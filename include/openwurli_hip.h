@@ -257,6 +257,54 @@ long long ow_batch_render_corrected(const ow_job* jobs, size_t n_jobs, const ow_
 long long ow_batch_render_mlp(const ow_job* jobs, size_t n_jobs, const ow_batch_cfg* cfg, const ow_mlp_weights* sets, size_t n_sets,
                               const uint32_t* set_of_job, double* out, size_t stride, int out_is_device);
 
+/* ---- training weight sets (ml/train_mlp.py's train(), many models per call) -----------------------------------------------------------
+ * One wavefront trains one model, its whole run inside one launch (k_mlp_train): per epoch the forward and backward pass over the
+ * model's train rows (masked Huber loss weighted per row, divided by the number of masked-in entries), torch.optim.Adam(lr,
+ * betas (0.9, 0.999), eps 1e-8, weight_decay as L2 in the gradient), the validation loss with the updated weights,
+ * ReduceLROnPlateau(min, sched_factor, sched_patience, threshold 1e-4 relative, min_lr, eps 1e-8) and early stopping after `patience`
+ * epochs without a strictly lower validation loss.  All arithmetic is f64; the result is deterministic and does not depend on the
+ * other models of the call. */
+typedef struct ow_mlp_train_model {        /* one model's hyper-parameters; train_mlp.py's flags */
+    double lr, min_lr, weight_decay, huber_delta, sched_factor;
+    uint32_t epochs, patience, sched_patience;
+    uint32_t target_mask;                  /* bit i set = target i is trained on (ANDed with the data's mask); --mask-decay-h3 clears bit 6 */
+} ow_mlp_train_model;
+typedef struct ow_mlp_train_cfg {
+    uint32_t struct_size, model_size;      /* sizeof(ow_mlp_train_cfg), sizeof(ow_mlp_train_model) */
+    int device;
+    uint32_t n_rows;
+    uint32_t history_epochs;               /* epochs per model in history_out; at least every model's `epochs` when history_out is given */
+    uint32_t reserved;
+    double* kernel_ms_out;                 /* NULL, or receives the time of k_mlp_train between two device events, in ms */
+} ow_mlp_train_cfg;
+typedef struct ow_mlp_train_result {
+    double best_val_loss, last_train_loss, last_val_loss, last_lr;     /* last_lr: the rate after the last epoch's scheduler step */
+    uint32_t best_epoch, epochs_run, lr_reductions;
+    uint32_t status;                       /* 0 = ok, 1 = no epoch ever improved (best_out = init) */
+} ow_mlp_train_result;
+/* The most row-epochs (n_rows x epochs) of one model: a model is one serial wavefront, and the launch is on a machine others share.
+ * Measured (tools/bench_mlp_train.py, one MI355X): 99 ns per row-epoch of a model running alone (2 000 epochs over 409 train and
+ * 103 validation rows in 101.7 ms), so a model at the cap whose train and validation rows together are n_rows (a split
+ * without overlap) holds its wavefront for about 6.7 s -- and for about 13 s where every row is in both parts (--no-split: an epoch
+ * walks 2 x n_rows rows, the cap counts n_rows); the instruction-count estimate behind the cap (1 400 multiply-adds per row-epoch at
+ * 32 per cycle) had said about one second. */
+#define OW_MLP_TRAIN_MAX_ROW_EPOCHS 67108864u      /* 2^26 */
+/* inputs [n_rows][2], targets [n_rows][11] (standardised), mask [n_rows][11] (non-zero = valid), row_weights [n_rows]: shared by all
+ * models.  split [n_models][n_rows]: bit 0 = train row, bit 1 = validation row of that model (80/20, no split, k-fold, leave-one-out
+ * are all rows of this table).  init [n_models]: the initial sets; their target_means / target_stds are copied into best_out unchanged,
+ * so best_out[i] is a set ow_mlp_infer / ow_batch_render_mlp take as it stands: the parameters after the epoch with the lowest
+ * validation loss.  history_out: NULL or [n_models][history_epochs][3] = train loss, validation loss, learning rate in force during
+ * the epoch's step; rows from a model's epochs_run on are 0.  Returns 0, <0 on error: everything is validated on the host before the
+ * device is touched (null pointers, n_rows == 0, non-finite data / weights / hyper-parameters, lr <= 0, huber_delta <= 0, sched_factor
+ * outside (0, 1), min_lr < 0, weight_decay < 0, epochs == 0, a model without a masked-in train or validation entry, more than 65535
+ * models, n_rows x epochs above OW_MLP_TRAIN_MAX_ROW_EPOCHS, history_epochs below a model's epochs, and two bounds on the call's
+ * memory: n_models x n_rows above 2^27 (the models' row lists: up to 1 GiB), n_models x history_epochs above 2^27 with history_out
+ * given (3 GiB)); ow_last_error() names model and field.  A masked-out entry and a lane past the end of a row list contribute exact
+ * zeros as long as the prediction is finite; once a model's weights have diverged, 0 x inf is NaN there as it is in torch. */
+int ow_mlp_train(const double* inputs, const double* targets, const uint8_t* mask, const double* row_weights, const uint8_t* split,
+                 const ow_mlp_weights* init, const ow_mlp_train_model* models, size_t n_models, const ow_mlp_train_cfg* cfg,
+                 ow_mlp_weights* best_out, ow_mlp_train_result* results, double* history_out);
+
 /* Plain device buffers for chaining the offline entry points without a host round trip (out_is_device / audio_is_device). */
 void* ow_device_alloc(size_t bytes, int device);   /* NULL on failure */
 void ow_device_free(void* ptr, int device);

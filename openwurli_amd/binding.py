@@ -44,6 +44,34 @@ class OwMlpCorrections(C.Structure):
     _fields_ = [("freq_offsets_cents", C.c_double * 5), ("decay_offsets", C.c_double * 5), ("ds_correction", C.c_double)]
 
 
+class OwMlpTrainModel(C.Structure):
+    """One model's hyper-parameters (ml/train_mlp.py's flags); target_mask bit i = target i is trained on."""
+    _fields_ = [("lr", C.c_double), ("min_lr", C.c_double), ("weight_decay", C.c_double), ("huber_delta", C.c_double), ("sched_factor", C.c_double),
+                ("epochs", C.c_uint32), ("patience", C.c_uint32), ("sched_patience", C.c_uint32), ("target_mask", C.c_uint32)]
+
+
+MLP_TRAIN_MODEL_DTYPE = [("lr", "<f8"), ("min_lr", "<f8"), ("weight_decay", "<f8"), ("huber_delta", "<f8"), ("sched_factor", "<f8"),
+                         ("epochs", "<u4"), ("patience", "<u4"), ("sched_patience", "<u4"), ("target_mask", "<u4")]
+MLP_TRAIN_MAX_ROW_EPOCHS = 1 << 26      # include/openwurli_hip.h OW_MLP_TRAIN_MAX_ROW_EPOCHS
+
+
+class OwMlpTrainCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("model_size", C.c_uint32), ("device", C.c_int), ("n_rows", C.c_uint32),
+                ("history_epochs", C.c_uint32), ("reserved", C.c_uint32), ("kernel_ms_out", C.POINTER(C.c_double))]
+
+    def __init__(self, n_rows=0, history_epochs=0, device=0, kernel_ms_out=None):
+        super().__init__(C.sizeof(OwMlpTrainCfg), C.sizeof(OwMlpTrainModel), device, n_rows, history_epochs, 0, kernel_ms_out)
+
+
+class OwMlpTrainResult(C.Structure):
+    _fields_ = [("best_val_loss", C.c_double), ("last_train_loss", C.c_double), ("last_val_loss", C.c_double), ("last_lr", C.c_double),
+                ("best_epoch", C.c_uint32), ("epochs_run", C.c_uint32), ("lr_reductions", C.c_uint32), ("status", C.c_uint32)]
+
+
+MLP_TRAIN_RESULT_DTYPE = [("best_val_loss", "<f8"), ("last_train_loss", "<f8"), ("last_val_loss", "<f8"), ("last_lr", "<f8"),
+                          ("best_epoch", "<u4"), ("epochs_run", "<u4"), ("lr_reductions", "<u4"), ("status", "<u4")]
+
+
 class OwMidiEvent(C.Structure):
     _fields_ = [("engine", C.c_uint32), ("type", C.c_uint8), ("note", C.c_uint8), ("reserved", C.c_uint16), ("value", C.c_float)]
 
@@ -346,6 +374,7 @@ SYMBOLS = {
     "ow_mlp_infer": (C.c_int, [_VP, C.c_size_t, _VP, _VP, C.c_size_t, C.c_int, _VP, _VP]),
     "ow_batch_render_corrected": (C.c_longlong, [C.POINTER(OwJob), C.c_size_t, C.POINTER(OwBatchCfg), _VP, _VP, C.c_size_t, C.c_int]),
     "ow_batch_render_mlp": (C.c_longlong, [C.POINTER(OwJob), C.c_size_t, C.POINTER(OwBatchCfg), _VP, C.c_size_t, _VP, _VP, C.c_size_t, C.c_int]),
+    "ow_mlp_train": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, C.POINTER(OwMlpTrainCfg), _VP, _VP, _VP]),
     "ow_device_alloc": (_VP, [C.c_size_t, C.c_int]),
     "ow_device_free": (None, [_VP, C.c_int]),
     "ow_host_alloc": (_VP, [C.c_size_t, C.c_int]),

@@ -13,8 +13,8 @@ void mlp_builtin(ow_mlp_weights& w) {
     std::memcpy(w.target_means, MLP_TARGET_MEANS, sizeof w.target_means); std::memcpy(w.target_stds, MLP_TARGET_STDS, sizeof w.target_stds);
 }
 
-// every weight of every set is finite; the refusal names the set and the field
-void check_weight_sets(const ow_mlp_weights* sets, size_t n_sets) {
+// every weight of every set is finite; the refusal names the set (what: "set ", or what the caller calls its sets) and the field
+void check_weight_sets(const ow_mlp_weights* sets, size_t n_sets, const char* what = "set ", const char* field_prefix = "") {
     struct Field { const char* name; size_t offset, rows, cols; };
     static const Field fields[] = {
         {"w1", offsetof(ow_mlp_weights, w1), 16, 2},   {"b1", offsetof(ow_mlp_weights, b1), 16, 0},
@@ -28,7 +28,7 @@ void check_weight_sets(const ow_mlp_weights* sets, size_t n_sets) {
             for (size_t k = 0; k < n; ++k)
                 if (!std::isfinite(v[k])) {
                     const std::string idx = f.cols ? "[" + std::to_string(k / f.cols) + "][" + std::to_string(k % f.cols) + "]" : "[" + std::to_string(k) + "]";
-                    throw std::runtime_error("set " + std::to_string(s) + ": " + f.name + idx + " is not finite");
+                    throw std::runtime_error(what + std::to_string(s) + ": " + field_prefix + f.name + idx + " is not finite");
                 }
         }
 }

@@ -25,6 +25,7 @@
 #include "ow_kernels.h"
 #include "ow_job_kernels.h"
 #include "ow_mlp_mfma.h"
+#include "ow_mlp_train.h"
 #include "ow_melange_dev.h"
 #include "ow_melange_lit.h"
 #include "ow_melange_col.h"
@@ -71,6 +72,7 @@ using owdev::OwEngineOut;
 #include "host/api_test_hooks.inc"      // C-ABI of include/openwurli_hip_test.h: host-logic hooks, diagnostics, switches
 #include "host/api_offline.inc"         // C-ABI: render_note, batch render, WAV writers, feature stage
 #include "host/api_mlp.inc"             // C-ABI: note-on MLP corrections given at run time (weight sets per job, explicit corrections)
+#include "host/api_mlp_train.inc"       // C-ABI: training note-on MLP weight sets on the device (ml/train_mlp.py's train(), many models per call)
 #include "host/api_alias_audit.inc"     // C-ABI: the click-band alias audit (alias_audit.rs)
 #include "host/api_midi_render.inc"     // C-ABI: `preamp-bench render-midi` (SMF reader, voice manager, chain)
 #include "host/api_calibrate.inc"       // C-ABI: `preamp-bench calibrate` / `sensitivity` (the calibration sweep)
