@@ -137,3 +137,126 @@ def run_power_amp(ow, name):
     res["resets"] = np.array([(g[k].diag().output_nan_resets, g[k].diag().preamp_nan_resets) for k in range(PA_ENGINES)], dtype=np.int64)
     g.close()
     return res
+
+
+# ---- the job-side chain kernels (k_job_chain<MEL>, _wide, _fused, _row, k_bark_chain_row, k_pbench<MEL>, k_pbench_row, k_poly_chain): what
+# tests/golden/job_chain_bits_parent.npz holds and tests/test_gpu_job_chain_bits.py renders again.  Each carries the same statements for a
+# fresh preamp's start, its step with the NaN reset, the half-band pairs and the output stage, so an edit made to all of them reaches
+# every form at once and the form-against-form tests cannot see it.
+JOB_DUR = 0.05                   # 2 205 samples at 44 100 Hz: a remainder against the chunk sizes 16, 24 and 64
+JOB_KEEP = 2205                  # samples of a kept row (a batch row whole; the head of a longer one)
+_ENV = ("OW_CHAIN_WIDE", "OW_JOB_FUSED", "OW_JOB_OVERLAP", "OW_JOB_ROW", "OW_BARK_ROW", "OW_BARK_CHUNK", "OW_PBENCH_ROW", "OW_PBENCH_CHUNK",
+        "OW_POLY_CHUNK", "OW_CENTROID_CHUNK")
+# tests/test_gpu_parity.py::test_chain_wide_is_bit_identical's five forced forms, and the library's own choice
+JOB_FORMS = {"default": {}, "0": {"OW_CHAIN_WIDE": "0", "OW_JOB_FUSED": "0"}, "1": {"OW_CHAIN_WIDE": "1"},
+             "1-quad": {"OW_CHAIN_WIDE": "1", "OW_JOB_ROW": "0"}, "1-one-wavefront": {"OW_CHAIN_WIDE": "1", "OW_JOB_FUSED": "0"},
+             "1-after-voices": {"OW_CHAIN_WIDE": "1", "OW_JOB_OVERLAP": "0"}}
+# static LDR values: no move, inside the 0.01 ohm hysteresis, below the 1 kohm clamp (the oracle runs it without a NaN reset), and the
+# cell's range as in test_chain_wide_is_bit_identical
+JOB_R = (1e6, 1e6 + 0.005, 500.0, 2.5e4, 1e6, 4e4, 1e5, 1e6, 7e5)
+_JOB_NOTES, _JOB_VELS = (33, 48, 60, 72, 84, 91, 96, 40, 55, 67, 79), (127, 50, 100, 20, 110, 64, 90, 35, 80)
+
+
+def batch_jobs():
+    """37 jobs = one lane-pair workgroup plus five, or four full row / quad workgroups plus a ragged one; mixed like
+    test_chain_wide_is_bit_identical's.  The last job's displacement scale is infinite: the reed signal is not finite, `main - shadow` is
+    not, and the adapter's NaN reset fires at every chain sample (the oracle does the same and renders silence) -- no other job-path test
+    reaches that branch, and a wrong value in it is replaced by the reset."""
+    jobs = [dict(note=_JOB_NOTES[k % 11], velocity=_JOB_VELS[k % 9], mlp=bool(k & 1), poweramp=bool(k & 2), volume=1.0 - 0.1 * (k % 4),
+                 speaker=0.25 * (k % 5), r_ldr=JOB_R[k % 9]) for k in range(37)]
+    jobs[36]["displacement_scale"] = float("inf")
+    return jobs
+
+
+# name -> (what, arguments)
+JOB_CASES = {}
+for _sr in (44100.0, 96000.0):                                   # 96 000 Hz: no oversampling
+    for _form in JOB_FORMS:
+        JOB_CASES[f"batch_{int(_sr)}_{_form}"] = ("batch", dict(sr=_sr, form=_form, kind=0, flags=False))
+# --no-preamp and --tremolo-depth: a call with a tremolo runs on k_job_chain<false> whatever the switches say
+JOB_CASES["batch_44100_flags"] = ("batch", dict(sr=44100.0, form="default", kind=0, flags=True))
+JOB_CASES["batch_44100_melange"] = ("batch", dict(sr=44100.0, form="default", kind=1, flags=False))
+for _kind, _rows in ((0, ("0", "1")), (1, (None,))):
+    for _row in _rows:
+        JOB_CASES[f"bark_{'melange' if _kind else 'legacy'}" + (f"_row{_row}" if _row else "")] = ("bark", dict(kind=_kind, row=_row))
+        JOB_CASES[f"pbench_{'melange' if _kind else 'legacy'}" + (f"_row{_row}" if _row else "")] = ("pbench", dict(kind=_kind, row=_row))
+JOB_CASES["poly"] = ("poly", {})
+JOB_CASES["centroid"] = ("centroid", {})
+
+
+def _rows_of(res, name, a, keep=(0, -1)):
+    """One SHA-256 per row of a [rows][...] block and the head of two rows."""
+    a = np.ascontiguousarray(a)
+    res[f"{name}_sha"] = np.stack([digest(r) for r in a])
+    for k in keep:
+        res[f"{name}_row{k % len(a)}"] = a[k].reshape(-1)[:JOB_KEEP].copy()
+
+
+def run_job_case(ow, name):
+    """Returns {array name: array}; `peak` is the largest magnitude of the case's audio."""
+    import os
+    what, arg = JOB_CASES[name]
+    saved = {k: os.environ.pop(k, None) for k in _ENV}
+    res = {}
+    try:
+        if what == "batch":
+            os.environ.update(JOB_FORMS[arg["form"]])
+            jobs = batch_jobs()
+            if arg["flags"]:
+                jobs = jobs[:5] + [dict(jobs[5], no_preamp=True), dict(jobs[6], tremolo_depth=0.5)]
+            out = ow.batch_render(jobs, arg["sr"], JOB_DUR, preamp_kind=arg["kind"])
+            assert out.shape == (len(jobs), int(JOB_DUR * arg["sr"]))
+            _rows_of(res, "out", out, keep=(0, len(jobs) - 2))          # the last job is the silent one
+            res["peak"] = np.array([np.abs(out).max()])
+            res["row_peaks"] = np.abs(out).max(axis=1)
+        elif what == "bark":
+            import bark_audit_ref
+            from openwurli_amd import bark_audit as ba
+            from openwurli_amd.intermod_audit import NOTE_JOB_DTYPE
+            notes, vels = (33, 41, 48, 57, 60, 66, 72, 79, 84, 90, 96), (127, 100, 80, 40, 20)      # test_gpu_bark_audit.py's _form_jobs(9)
+            jobs = np.zeros(9, dtype=NOTE_JOB_DTYPE)
+            jobs["note"], jobs["velocity"] = [notes[i % 11] for i in range(9)], [vels[i % 5] for i in range(9)]
+            if arg["row"] is not None:
+                os.environ["OW_BARK_ROW"] = arg["row"]
+            rows, taps = ba.run_jobs(jobs, arg["kind"], *bark_audit_ref.SHORT_SIZE, taps=True)
+            res["rows"] = np.frombuffer(rows.tobytes(), dtype=np.uint8).copy()
+            res["taps_sha"] = np.stack([digest(r) for r in taps])      # per job: reed, pickup and preamp taps
+            _rows_of(res, "pre", taps[:, 2])                           # the tap behind the chain, two rows whole
+            res["peak"] = np.array([np.abs(taps[:, 2]).max()])
+        elif what == "pbench":
+            from openwurli_amd import preamp_bench as pb
+            freqs = [20.0, 55.0, 110.0, 220.0, 440.0, 1000.0, 2000.0, 5000.0, 10000.0, 15000.0, 20000.0]
+            amps = [0.001, 0.005, 0.02, 0.001, 0.05, 0.001, 0.005, 0.001, 0.02, 0.001, 0.005]
+            r = [JOB_R[k % 9] for k in range(11)]
+            r_reset = [1e6, 1e6, 1e6, 1.9e4, 2.5e4, 500.0, 1e5, 1e6 + 0.005, 7e5, 1e6, 4e4]          # differs from r_ldr on seven points
+            if arg["row"] is not None:
+                os.environ["OW_PBENCH_ROW"] = arg["row"]
+            rows, trace = pb.run_points(pb.make_points(freqs, amps, r, r_reset), arg["kind"], trace=True)
+            res["rows"] = np.frombuffer(rows.tobytes(), dtype=np.uint8).copy()
+            _rows_of(res, "trace", trace)
+            res["peak"] = np.array([np.abs(trace).max()])
+        elif what == "poly":
+            from openwurli_amd import render_poly as rp
+            # the command's measuring window starts at sample 8 820, so a chord cannot be shorter than 0.2 s: 0.21 s = 9 261 samples
+            chords = [((60,), (100,), 0.6, 1.0, 1e6, False), ((48, 55), (90, 70), 0.8, 0.5, 500.0, True), ((38, 59, 62), (45, 40, 110), 1.0, 0.0, 4e4, False)]
+            rows, audio = rp.run_chords(chords, 0.21, final=True, separate_sum=True, residual=True)
+            res["rows"] = np.frombuffer(rows.tobytes(), dtype=np.uint8).copy()
+            for k, a in audio.items():
+                _rows_of(res, k, a)
+            res["peak"] = np.array([np.abs(audio["final"]).max()])
+        elif what == "centroid":
+            from openwurli_amd import centroid_track as ct
+            # set_ldr_resistance(r) before reset(): the DC solve runs at the clamped --ldr
+            jobs = [dict(note=n, velocity=v, ldr=r) for n, v, r in ((60, 100, 1e6), (33, 127, 1e6 + 0.005), (96, 110, 500.0), (72, 64, 2.5e4))]
+            jobs.append(dict(note=48, velocity=90, ldr=7e5, no_preamp=True))
+            rows, frames, audio = ct.run_jobs(jobs, JOB_DUR, end_ms=40.0, audio=True)
+            res["rows"] = np.frombuffer(rows.tobytes(), dtype=np.uint8).copy()
+            res["frames"] = frames.copy()
+            _rows_of(res, "audio", audio)
+            res["peak"] = np.array([np.abs(audio).max()])
+    finally:
+        for k in _ENV:
+            os.environ.pop(k, None)
+            if saved[k] is not None:
+                os.environ[k] = saved[k]
+    return res
