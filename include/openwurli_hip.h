@@ -346,6 +346,44 @@ typedef struct ow_segment {
 int ow_extract_harmonics(const double* audio, size_t n_rows, size_t stride, double sample_rate, const ow_segment* segs, size_t n_segs,
                          double search_pct, int wav24_mode, int device, int audio_is_device, double* amps, double* freqs, double* rms);
 
+/* ---- the recording side of the ML loop: stage 3 (ml/extract_harmonics.py) and stage 5 (ml/compute_residuals.py) ---- */
+/* What the two entry points below share.  audio is f64 [n_rows][stride], a device pointer if audio_is_device != 0; wav24_mode as for
+ * ow_extract_harmonics. */
+typedef struct ow_harmonics_cfg {
+    uint32_t struct_size;   /* sizeof(ow_harmonics_cfg) */
+    uint32_t segment_size;  /* sizeof(ow_segment) */
+    double sample_rate;
+    double search_pct;      /* ow_goertzel_harmonics: half-width of the offset search (the reference's 0.01); ow_interharmonic_noise ignores it */
+    int wav24_mode;         /* OW_WAV_NONE / OW_WAV_ROUND / OW_WAV_TRUNCATE */
+    int device;
+    int audio_is_device;
+    int reserved;           /* 0 */
+} ow_harmonics_cfg;
+/* extract_harmonics_goertzel (ml/goertzel_utils.py:34-57, 106-119) on many segments at once, the Goertzel counterpart of
+ * ow_extract_harmonics.  Per harmonic h*f0 below sr/2 - 100 Hz: the OW_GOERTZEL_OFFSETS offsets of np.linspace(-search_pct, search_pct, 11)
+ * (start + i*step, the last one search_pct itself), f = h*f0 * (1.0 + offset), k = nearbyint(f * N / sr) (half to even, as Python's round
+ * of a float64), skipped if k <= 0 or k >= N / 2; coeff = 2.0 * cos(2.0 * pi * k / N); the recurrence s0 = (x + coeff*s1) - s2 over the N
+ * samples of the segment, every operation a single rounded f64 operation on the device; magnitude sqrt(s1*s1 + s2*s2 - coeff*s1*s2) / N * 2.0;
+ * the first maximum over the offsets (strict >, starting from 0.0), floored at 1e-20.  Harmonics at or above sr/2 - 100 Hz report 1e-20.
+ * Offsets of one harmonic that round to the same k run once: the same k gives the same (s1, s2) and a strict > ignores repeats.
+ * amps: [n_segs][OW_MAX_HARMONICS] (entries past n_harmonics are 0).
+ * coeffs_out / bins_out: NULL, or [n_segs][OW_MAX_HARMONICS][OW_GOERTZEL_OFFSETS]: the coefficient and the bin k of every offset as
+ * the library used them (k = -1 and coefficient 0 where the offset was skipped, the harmonic lies past the cut or past n_harmonics).
+ * Refuses (<0, ow_last_error() says why): a null argument, sizes that do not match this header, an unknown wav24_mode, a sample rate or
+ * search_pct that is not finite and positive / non-negative, a segment out of range, longer than 2^22 samples or with an f0 that is not
+ * finite.  n_segs == 0 returns 0. */
+#define OW_GOERTZEL_OFFSETS 11
+int ow_goertzel_harmonics(const double* audio, size_t n_rows, size_t stride, const ow_segment* segs, size_t n_segs, const ow_harmonics_cfg* cfg,
+                          double* amps, double* coeffs_out, int32_t* bins_out);
+/* The noise floor of measure_interharmonic_snr (ml/compute_residuals.py:93-117) of many segments at once: for h = 0..n_harmonics-1 the
+ * np.median of the Hann-windowed, 4x zero-padded spectrum (scaled 2 / N / 0.5) over the bins inside [0.99, 1.01] x (h + 1.5) x f0, floored
+ * at 1e-20; 1e-20 where (h + 1.5) x f0 >= sr/2 - 100 Hz or no bin lies in the band.  noise: [n_segs][OW_MAX_HARMONICS] (entries past
+ * n_harmonics are 0).  Refuses what ow_goertzel_harmonics refuses, and a segment one of whose bands holds more than OW_NOISE_MAX_BAND_BINS
+ * bins (the band's magnitudes are held on chip; the reference's 0.15 s window reaches about 260).  n_segs == 0 returns 0. */
+#define OW_NOISE_MAX_BAND_BINS 4096
+int ow_interharmonic_noise(const double* audio, size_t n_rows, size_t stride, const ow_segment* segs, size_t n_segs, const ow_harmonics_cfg* cfg,
+                           double* noise);
+
 /* ---- click-band alias audit (crates/openwurli-dsp/src/alias_audit.rs) ----------- */
 /* AliasAuditResult (alias_audit.rs:68-93), same fields in the same order. */
 #define OW_AUDIT_HARMONICS 12

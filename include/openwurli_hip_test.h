@@ -156,6 +156,8 @@ int ow_test_engine_read_preamp_state(ow_engine*, int shadow, double* out14);
 
 /* Plain device-to-host copy, for reading a block that ow_pool_render(pool, NULL, ...) left in HBM (ow_pool_device_output). */
 int ow_test_device_read(void* dst_host, const void* src_device, size_t bytes, int device);
+/* Plain host-to-device copy into a buffer of ow_device_alloc, for handing given audio to an entry point's audio_is_device path. */
+int ow_test_device_write(void* dst_device, const void* src_host, size_t bytes, int device);
 
 /* k_window_stats (the analysis kernel of ow_overshoot) on given host rows: signals f64 [n_rows][stride]; up to four windows [starts[k],
  * ends[k]) with ends[k] <= stride, kinds[k] 0 = max |x| (NaN samples ignored, an empty window gives 0), 1 = sum of squares; out host f64

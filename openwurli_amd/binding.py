@@ -312,6 +312,17 @@ class OwSegment(C.Structure):
 SEGMENT_DTYPE = [("row", "<u4"), ("start", "<u4"), ("end", "<u4"), ("n_harmonics", "<u4"), ("f0", "<f8")]
 MAX_HARMONICS = 8
 WAV_NONE, WAV_ROUND, WAV_TRUNCATE = -1, 0, 1
+GOERTZEL_OFFSETS = 11            # include/openwurli_hip.h OW_GOERTZEL_OFFSETS
+NOISE_MAX_BAND_BINS = 4096       # include/openwurli_hip.h OW_NOISE_MAX_BAND_BINS
+
+
+class OwHarmonicsCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("segment_size", C.c_uint32), ("sample_rate", C.c_double), ("search_pct", C.c_double),
+                ("wav24_mode", C.c_int), ("device", C.c_int), ("audio_is_device", C.c_int), ("reserved", C.c_int)]
+
+    def __init__(self, sample_rate=44100.0, search_pct=0.01, wav24_mode=WAV_NONE, device=0, audio_is_device=0):
+        super().__init__(C.sizeof(OwHarmonicsCfg), 24, sample_rate, search_pct, wav24_mode, device, audio_is_device, 0)
+
 
 SYMBOLS = {
     "ow_abi_version": (C.c_int, []),
@@ -383,6 +394,8 @@ SYMBOLS = {
     "ow_wav24_write": (C.c_int, [C.c_char_p, _VP, C.c_size_t, C.c_uint32, C.c_double, C.c_int]),
     "ow_extract_harmonics": (C.c_int, [_VP, C.c_size_t, C.c_size_t, C.c_double, _VP, C.c_size_t, C.c_double, C.c_int, C.c_int, C.c_int,
                                        _VP, _VP, _VP]),
+    "ow_goertzel_harmonics": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, C.c_size_t, C.POINTER(OwHarmonicsCfg), _VP, _VP, _VP]),
+    "ow_interharmonic_noise": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, C.c_size_t, C.POINTER(OwHarmonicsCfg), _VP]),
     "ow_alias_audit_analyze": (C.c_int, [_VP, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, _VP, C.c_int, C.c_int, _VP]),
     "ow_alias_audit_run": (C.c_int, [_VP, _VP, C.c_size_t, C.c_int, C.c_int, _VP, _VP, C.c_size_t]),
     "ow_smf_parse": (C.c_longlong, [_VP, C.c_size_t, C.c_int, _VP, C.c_size_t]),
@@ -436,6 +449,7 @@ TEST_SYMBOLS = {
     "ow_test_pool_trajectory_state": (C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     "ow_test_host_melange_paths": (C.c_int, [C.c_double]),
     "ow_test_device_read": (C.c_int, [_VP, _VP, C.c_size_t, C.c_int]),
+    "ow_test_device_write": (C.c_int, [_VP, _VP, C.c_size_t, C.c_int]),
     "ow_debug_window_stats": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, _VP, _VP, C.c_size_t, C.c_int, _VP]),
     "ow_debug_note_table": (C.c_int, [_VP, C.c_int]),
     "ow_test_engine_poke_voice": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, C.c_double]),

@@ -235,13 +235,7 @@ int ow_extract_harmonics(const double* audio, size_t n_rows, size_t stride, doub
                 const double fh = g.f0 * (double)(h + 1);
                 if (!(fh >= sample_rate / 2 - 100)) {
                     const double f_lo = fh * (1.0 - search_pct), f_hi = fh * (1.0 + search_pct);
-                    double q = f_lo / val;
-                    uint64_t k = (q > 0.0 && q < (double)nb) ? (uint64_t)q : (q >= (double)nb ? nb : 0);
-                    while (k > 0 && (double)(k - 1) * val >= f_lo) --k;
-                    while (k < nb && (double)k * val < f_lo) ++k;
-                    const uint64_t k_lo = k;
-                    while (k < nb && (double)k * val <= f_hi) ++k;
-                    if (k > k_lo) { b.k_lo = (uint32_t)k_lo; b.k_hi = (uint32_t)(k - 1); }
+                    feat_band_bins(val, nb, f_lo, f_hi, b.k_lo, b.k_hi);
                 }
                 hb.push_back(b);
             }

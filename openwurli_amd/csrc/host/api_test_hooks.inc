@@ -223,6 +223,12 @@ int ow_test_device_read(void* dst_host, const void* src_device, size_t bytes, in
     if (hipSetDevice(device) != hipSuccess) return -1;
     return hipMemcpy(dst_host, src_device, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
+// plain host-to-device copy (tests hand given audio to the audio_is_device paths)
+int ow_test_device_write(void* dst_device, const void* src_host, size_t bytes, int device) {
+    if (!dst_device || !src_host) return -1;
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    return hipMemcpy(dst_device, src_host, bytes, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
 #ifdef OW_DBG_COUNTERS
 // development counters (built with OW_HIPCC_EXTRA=-DOW_DBG_COUNTERS only): read and clear
 extern "C" int ow_debug_counters(unsigned long long* out8, int device) {

@@ -51,6 +51,17 @@ size_t budget_chunk(size_t budget_bytes, size_t bytes_per_item, long long cap, s
     if (cap > 0) c = std::min(c, (size_t)cap);
     return std::max<size_t>(std::min(c, n_items), 1);
 }
+// bins k of numpy's frequency axis (k * val, k < nb) with f_lo <= k * val <= f_hi, numpy's own arithmetic: k_lo..k_hi inclusive; both are
+// left as they are (the callers' "no bin" state, k_lo > k_hi) when the mask is empty
+inline void feat_band_bins(double val, uint64_t nb, double f_lo, double f_hi, uint32_t& k_lo_out, uint32_t& k_hi_out) {
+    double q = f_lo / val;
+    uint64_t k = (q > 0.0 && q < (double)nb) ? (uint64_t)q : (q >= (double)nb ? nb : 0);
+    while (k > 0 && (double)(k - 1) * val >= f_lo) --k;
+    while (k < nb && (double)k * val < f_lo) ++k;
+    const uint64_t k_lo = k;
+    while (k < nb && (double)k * val <= f_hi) ++k;
+    if (k > k_lo) { k_lo_out = (uint32_t)k_lo; k_hi_out = (uint32_t)(k - 1); }
+}
 // rows of n doubles, dev_stride_doubles apart on the device -> host rows host_stride doubles apart, on st (no synchronisation)
 void rows_to_host(double* host, size_t host_stride, const void* dev, size_t dev_stride_doubles, size_t n, size_t rows, hipStream_t st) {
     HIP_OK(hipMemcpy2DAsync(host, host_stride * sizeof(double), dev, dev_stride_doubles * sizeof(double), n * sizeof(double), rows, hipMemcpyDeviceToHost, st));

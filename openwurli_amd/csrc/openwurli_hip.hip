@@ -32,6 +32,7 @@
 #include "ow_melange_eng.h"
 #include "ow_power_amp_dev.h"
 #include "ow_features.h"
+#include "ow_goertzel_kernels.h"
 #include "ow_trem_wide.h"
 #include "ow_trem_row.h"
 #include "ow_chain_row.h"
@@ -82,3 +83,4 @@ using owdev::OwEngineOut;
 #include "host/api_note_audit.inc"      // C-ABI: `preamp-bench intermod-audit` / `overshoot` (the note audits, many notes per call)
 #include "host/api_bark_audit.inc"      // C-ABI: `preamp-bench bark-audit` (H2 / H1 per chain stage, many notes per call)
 #include "host/api_pump.inc"            // C-ABI: `preamp-bench pump-sweep` / `pump-trace` / `pump-spike` / `pump-step` / `pump-sinusoid` (the pump measurements)
+#include "host/api_harmonics.inc"       // C-ABI: the recording side of the ML loop (Goertzel harmonics, inter-harmonic noise floor; many segments per call)

@@ -53,7 +53,53 @@ def write_wav_24bit(path, samples, sample_rate, scale=1.0, mode="round"):
 _WAV_MODES = {None: binding.WAV_NONE, "round": binding.WAV_ROUND, "truncate": binding.WAV_TRUNCATE}
 
 
-def extract_segments(audio, sample_rate, segments, search_pct=0.01, device=0, wav24=None, device_audio=None):
+def _audio_args(audio, device_audio):
+    """(pointer, rows, stride, audio_is_device, the array that keeps the pointer alive)."""
+    if device_audio is None:
+        a = np.ascontiguousarray(audio, dtype=np.float64)
+        if a.ndim == 1:
+            a = a[None, :]
+        return a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], 0, a
+    return C.c_void_p(int(device_audio[0])), int(device_audio[1]), int(device_audio[2]), 1, None
+
+
+def _segment_array(segments):
+    return np.array([tuple(s) for s in segments], dtype=np.dtype(binding.SEGMENT_DTYPE))
+
+
+def goertzel_segments(audio, sample_rate, segments, search_pct=0.01, device=0, wav24=None, device_audio=None, plan=False):
+    """`extract_harmonics_goertzel` (goertzel_utils.py:106-119) on many segments in one call (ow_goertzel_harmonics); arguments as
+    extract_segments.  Returns amps [n, 8]; with plan=True also the coefficients [n, 8, 11] and bins [n, 8, 11] (-1: skipped) of every
+    offset as the library used them."""
+    lib = binding.load_library()
+    ptr, rows, stride, on_dev, _keep = _audio_args(audio, device_audio)
+    seg = _segment_array(segments)
+    n = seg.size
+    amps = np.zeros((n, binding.MAX_HARMONICS))
+    coeffs = np.zeros((n, binding.MAX_HARMONICS, binding.GOERTZEL_OFFSETS))
+    bins = np.full((n, binding.MAX_HARMONICS, binding.GOERTZEL_OFFSETS), -1, dtype=np.int32)
+    cfg = binding.OwHarmonicsCfg(float(sample_rate), float(search_pct), _WAV_MODES[wav24], int(device), on_dev)
+    rc = lib.ow_goertzel_harmonics(ptr, rows, stride, seg.ctypes.data_as(C.c_void_p), n, C.byref(cfg), amps.ctypes.data_as(C.c_void_p),
+                                   coeffs.ctypes.data_as(C.c_void_p) if plan else None, bins.ctypes.data_as(C.c_void_p) if plan else None)
+    if rc != 0:
+        raise OwError(binding.take_error(lib))
+    return (amps, coeffs, bins) if plan else amps
+
+
+def noise_segments(audio, sample_rate, segments, device=0, wav24=None, device_audio=None):
+    """The inter-harmonic noise floor of measure_interharmonic_snr (compute_residuals.py:93-117) on many segments in one call
+    (ow_interharmonic_noise): noise [n, 8], the median of the spectrum around (h + 1.5) * f0."""
+    lib = binding.load_library()
+    ptr, rows, stride, on_dev, _keep = _audio_args(audio, device_audio)
+    seg = _segment_array(segments)
+    noise = np.zeros((seg.size, binding.MAX_HARMONICS))
+    cfg = binding.OwHarmonicsCfg(float(sample_rate), 0.01, _WAV_MODES[wav24], int(device), on_dev)
+    if lib.ow_interharmonic_noise(ptr, rows, stride, seg.ctypes.data_as(C.c_void_p), seg.size, C.byref(cfg), noise.ctypes.data_as(C.c_void_p)) != 0:
+        raise OwError(binding.take_error(lib))
+    return noise
+
+
+def extract_segments(audio, sample_rate, segments, search_pct=0.01, device=0, wav24=None, device_audio=None, method="fft"):
     """`extract_harmonics_fft` on many segments in one call.
 
     audio: float64 [rows, stride]; segments: iterable of (row, start, end, n_harmonics, f0).
@@ -61,16 +107,21 @@ def extract_segments(audio, sample_rate, segments, search_pct=0.01, device=0, wa
     reads back as (the reference script always goes through the file).
     device_audio = (pointer, rows, stride): analyse f64 audio that is already in HBM (e.g. what batch_render left there) instead of
     `audio` (which may then be None).
+    method: "fft" (extract_harmonics_fft) or "goertzel" (extract_harmonics_goertzel: freqs are the nominal (h + 1) * f0 the reference's
+    caller reports, rms is not measured and comes back as zeros).
     Returns (amps [n, 8], freqs [n, 8], rms [n])."""
+    if method == "goertzel":
+        segments = list(segments)
+        amps = goertzel_segments(audio, sample_rate, segments, search_pct, device, wav24, device_audio)
+        freqs = np.zeros_like(amps)
+        for i, s in enumerate(segments):
+            freqs[i, :s[3]] = [s[4] * (h + 1) for h in range(s[3])]
+        return amps, freqs, np.zeros(len(segments))
+    if method != "fft":
+        raise ValueError(f"unknown method {method!r}: \"fft\" or \"goertzel\"")
     lib = binding.load_library()
-    if device_audio is None:
-        a = np.ascontiguousarray(audio, dtype=np.float64)
-        if a.ndim == 1:
-            a = a[None, :]
-        ptr, rows, stride, on_dev = a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], 0
-    else:
-        ptr, rows, stride, on_dev = C.c_void_p(int(device_audio[0])), int(device_audio[1]), int(device_audio[2]), 1
-    seg = np.array([tuple(s) for s in segments], dtype=np.dtype(binding.SEGMENT_DTYPE))
+    ptr, rows, stride, on_dev, _keep = _audio_args(audio, device_audio)
+    seg = _segment_array(segments)
     n = seg.size
     amps = np.zeros((n, binding.MAX_HARMONICS)); freqs = np.zeros((n, binding.MAX_HARMONICS)); rms = np.zeros(n)
     if n == 0:
@@ -88,6 +139,12 @@ def extract_harmonics_fft(signal, sr, f0, n_harmonics=8, search_pct=0.01, device
     x = np.ascontiguousarray(signal, dtype=np.float64)
     amps, freqs, _ = extract_segments(x[None, :], sr, [(0, 0, x.size, n_harmonics, f0)], search_pct, device)
     return amps[0, :n_harmonics].copy(), freqs[0, :n_harmonics].copy()
+
+
+def extract_harmonics_goertzel(signal, sr, f0, n_harmonics=8, search_pct=0.01, device=0):
+    """Drop-in for goertzel_utils.extract_harmonics_goertzel: amps of H1..Hn of one signal."""
+    x = np.ascontiguousarray(signal, dtype=np.float64)
+    return goertzel_segments(x[None, :], sr, [(0, 0, x.size, n_harmonics, f0)], search_pct, device)[0, :n_harmonics].copy()
 
 
 def _note_segments(row, n_samples, sr, f0):
