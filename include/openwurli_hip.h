@@ -384,6 +384,51 @@ int ow_goertzel_harmonics(const double* audio, size_t n_rows, size_t stride, con
 int ow_interharmonic_noise(const double* audio, size_t n_rows, size_t stride, const ow_segment* segs, size_t n_segs, const ow_harmonics_cfg* cfg,
                            double* noise);
 
+/* ---- recorded-note intake: stage 2 (ml/score_isolation.py) and the non-neural half of stage 1 (ml/extract_notes.py) ---- */
+/* One note of score_notes' list.  window_start / window_end: the analysis window as score_notes (score_isolation.py:266-271) plans it,
+ * computed by the caller.  id_key stands for the note's "id": equal strings, equal keys (an other is skipped by id equality, :43, not by
+ * position).  score == 0: the reference does not score this note (obm_isolated, duration score 0); it still counts as an other. */
+typedef struct ow_iso_note {
+    double onset_s, offset_s, amplitude;
+    double window_start, window_end;
+    int64_t id_key;
+    int32_t midi_note;      /* 0..127 */
+    int32_t score;
+} ow_iso_note;
+typedef struct ow_iso_cfg {
+    uint32_t struct_size;        /* sizeof(ow_iso_cfg) */
+    uint32_t note_size;          /* sizeof(ow_iso_note) */
+    int device;
+    int reserved;                /* 0 */
+    double collision_ratio;      /* 2.0 ** (50.0 / 1200.0), score_isolation.py:79 */
+    const double* decay_rate;    /* [128]: 0.26 * exp(0.049 * midi), :31, in the caller's own libm */
+    const double* midi_freq;     /* [128]: midi_to_freq (ml/goertzel_utils.py:129-131), in the caller's own libm */
+    double* kernel_ms_out;       /* NULL, or where the kernel's device time goes (0 when no kernel ran) */
+} ow_iso_cfg;
+/* harmonic_collision_check (ml/score_isolation.py:69-102) of one target against one other, for all pairs of MIDI numbers:
+ * table[target * 128 + other], bit h set while harmonic h + 1 of the target is clean.  Host arithmetic only (multiply, divide, max, min,
+ * compare): no device needed.  Refuses a null argument and a non-finite frequency or ratio. */
+int ow_isolation_collision_table(const double* midi_freq, double collision_ratio, uint8_t* table);
+/* score_temporal, score_harmonic_collision and score_energy_dominance (ml/score_isolation.py:36-167) for all notes of all files in one
+ * call.  notes[file_first[f] .. file_first[f + 1]) are the notes of file f in their order in the caller's list, which is the order the
+ * sums run in (file_first has n_files + 1 entries, from 0 to n_notes).  Per scored note, unrounded: temporal (after the 0.05 floor),
+ * collision (clean weight / 12), dominance, and mask (bit h: harmonic h + 1 clean; no energetic other: 0xFF and collision 1.0); zeros
+ * for a note with score == 0.  remaining = pow(10.0, -(rate * t) / 20.0) is the device library's pow; everything else is the reference's
+ * arithmetic operation for operation, every comparison strict as there.
+ * Refuses (<0, ow_last_error() says why): a null argument, sizes that do not match this header, a midi_note outside 0..127, a
+ * non-finite time, amplitude, window or table entry, file ranges that are not ascending or do not cover the notes.  n_notes == 0
+ * returns 0. */
+int ow_isolation_score(const ow_iso_note* notes, size_t n_notes, const uint64_t* file_first, size_t n_files, const ow_iso_cfg* cfg,
+                       double* temporal, double* collision, double* dominance, uint8_t* mask);
+/* detect_obm_onset / detect_obm_offset (ml/extract_notes.py:43-64) and the onset search of extract_sustain_window
+ * (ml/goertzel_utils.py:139-153) on many clips at once.  clips: host f64 [n_clips][stride]; lengths[c] <= stride samples of row c are
+ * audio, the rest of the row is not read.  Per clip: peak = max |x| (0 for an empty clip), first = the first index with
+ * |x| > onset_frac * peak, last = the last index >= 1 with |x| > offset_frac * peak (the reference's backward loop stops before index 0);
+ * -1: none.  Each threshold is the one product, each comparison strict.  Seconds and the fallbacks (peak < 1e-10, none found) are the
+ * caller's.  Refuses a null argument, a non-finite fraction, a stride of 0 and a length above the stride.  n_clips == 0 returns 0. */
+int ow_clip_bounds(const double* clips, size_t n_clips, size_t stride, const uint32_t* lengths, double onset_frac, double offset_frac, int device,
+                   double* peak, int64_t* first, int64_t* last);
+
 /* ---- click-band alias audit (crates/openwurli-dsp/src/alias_audit.rs) ----------- */
 /* AliasAuditResult (alias_audit.rs:68-93), same fields in the same order. */
 #define OW_AUDIT_HARMONICS 12

@@ -24,5 +24,7 @@ from .mlp import MlpWeights  # noqa: F401
 from . import mlp_train  # noqa: F401
 from . import harmonics  # noqa: F401
 from . import residuals  # noqa: F401
+from . import isolation  # noqa: F401
+from . import note_intake  # noqa: F401
 
-__all__ = ["load_library", "library_path", "OwError", "WurliEngine", "EnginePool", "VoiceState", "render_note", "batch_render", "normalize_scale", "tremolo_prefetch", "tremolo_configure", "tremolo_export", "tremolo_import", "features", "alias_audit", "midi_render", "calibrate", "preamp_bench", "render_poly", "centroid_track", "intermod_audit", "overshoot", "pump", "bark_audit", "mlp", "MlpWeights", "mlp_train", "harmonics", "residuals"]
+__all__ = ["load_library", "library_path", "OwError", "WurliEngine", "EnginePool", "VoiceState", "render_note", "batch_render", "normalize_scale", "tremolo_prefetch", "tremolo_configure", "tremolo_export", "tremolo_import", "features", "alias_audit", "midi_render", "calibrate", "preamp_bench", "render_poly", "centroid_track", "intermod_audit", "overshoot", "pump", "bark_audit", "mlp", "MlpWeights", "mlp_train", "harmonics", "residuals", "isolation", "note_intake"]

@@ -324,6 +324,24 @@ class OwHarmonicsCfg(C.Structure):
         super().__init__(C.sizeof(OwHarmonicsCfg), 24, sample_rate, search_pct, wav24_mode, device, audio_is_device, 0)
 
 
+class OwIsoNote(C.Structure):
+    _fields_ = [("onset_s", C.c_double), ("offset_s", C.c_double), ("amplitude", C.c_double), ("window_start", C.c_double),
+                ("window_end", C.c_double), ("id_key", C.c_int64), ("midi_note", C.c_int32), ("score", C.c_int32)]
+
+
+ISO_NOTE_DTYPE = [("onset_s", "<f8"), ("offset_s", "<f8"), ("amplitude", "<f8"), ("window_start", "<f8"), ("window_end", "<f8"),
+                  ("id_key", "<i8"), ("midi_note", "<i4"), ("score", "<i4")]
+
+
+class OwIsoCfg(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("note_size", C.c_uint32), ("device", C.c_int), ("reserved", C.c_int),
+                ("collision_ratio", C.c_double), ("decay_rate", C.POINTER(C.c_double)), ("midi_freq", C.POINTER(C.c_double)),
+                ("kernel_ms_out", C.POINTER(C.c_double))]
+
+    def __init__(self, collision_ratio=0.0, decay_rate=None, midi_freq=None, device=0, kernel_ms_out=None):
+        super().__init__(C.sizeof(OwIsoCfg), C.sizeof(OwIsoNote), device, 0, collision_ratio, decay_rate, midi_freq, kernel_ms_out)
+
+
 SYMBOLS = {
     "ow_abi_version": (C.c_int, []),
     "ow_last_error": (C.c_char_p, []),
@@ -396,6 +414,9 @@ SYMBOLS = {
                                        _VP, _VP, _VP]),
     "ow_goertzel_harmonics": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, C.c_size_t, C.POINTER(OwHarmonicsCfg), _VP, _VP, _VP]),
     "ow_interharmonic_noise": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, C.c_size_t, C.POINTER(OwHarmonicsCfg), _VP]),
+    "ow_isolation_collision_table": (C.c_int, [_VP, C.c_double, _VP]),
+    "ow_isolation_score": (C.c_int, [_VP, C.c_size_t, _VP, C.c_size_t, C.POINTER(OwIsoCfg), _VP, _VP, _VP, _VP]),
+    "ow_clip_bounds": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, C.c_double, C.c_double, C.c_int, _VP, _VP, _VP]),
     "ow_alias_audit_analyze": (C.c_int, [_VP, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, _VP, C.c_int, C.c_int, _VP]),
     "ow_alias_audit_run": (C.c_int, [_VP, _VP, C.c_size_t, C.c_int, C.c_int, _VP, _VP, C.c_size_t]),
     "ow_smf_parse": (C.c_longlong, [_VP, C.c_size_t, C.c_int, _VP, C.c_size_t]),

@@ -33,6 +33,7 @@
 #include "ow_power_amp_dev.h"
 #include "ow_features.h"
 #include "ow_goertzel_kernels.h"
+#include "ow_isolation_kernels.h"
 #include "ow_trem_wide.h"
 #include "ow_trem_row.h"
 #include "ow_chain_row.h"
@@ -84,3 +85,4 @@ using owdev::OwEngineOut;
 #include "host/api_bark_audit.inc"      // C-ABI: `preamp-bench bark-audit` (H2 / H1 per chain stage, many notes per call)
 #include "host/api_pump.inc"            // C-ABI: `preamp-bench pump-sweep` / `pump-trace` / `pump-spike` / `pump-step` / `pump-sinusoid` (the pump measurements)
 #include "host/api_harmonics.inc"       // C-ABI: the recording side of the ML loop (Goertzel harmonics, inter-harmonic noise floor; many segments per call)
+#include "host/api_isolation.inc"       // C-ABI: recorded-note intake (isolation sub-scores of all notes of all files per call, clip bounds of many clips per call)
