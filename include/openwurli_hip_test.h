@@ -154,6 +154,31 @@ int ow_test_engine_poke_preamp_node(ow_engine*, int shadow, int node, double vol
  * dk_preamp_legacy.rs:231-239).  Returns 0, <0 on error. */
 int ow_test_engine_read_preamp_state(ow_engine*, int shadow, double* out14);
 
+/* ---- chain-state rows ---------------------------------------------------------------------------- */
+/* Rows [first_row, first_row + n_rows) of engine e's chain state (CS_* of openwurli_amd/csrc/ow_types.h, one double each; u64 rows as
+ * their bits) copied out to / in from n_rows doubles.  The output stage -- power amp, half-band decimator, speaker, the two smoothers,
+ * f32 cast and NaN guard -- keeps all it carries from block to block in the rows named here, so "rows before + the stage's input
+ * (ow_pool_read_preamp_out / ow_test_pool_read_power_amp_out) + setters -> rows after + f32 block" is a pure function that
+ * tests/test_gpu_post_stage.py compares with the oracle's (owo_output_stage_block).  The write forgets a block rendered ahead and waits
+ * for the stream first; the host's own mirror of a smoother's target is not touched, so write the target it holds.  Both refuse rows
+ * outside [0, OW_TEST_CS_COUNT).  Return 0, <0 on error. */
+#define OW_TEST_CS_SM_SPK 22   /* [4] speaker-character smoother: current, target, step, remaining (u64) */
+#define OW_TEST_CS_SM_VOL 26   /* [4] volume smoother */
+#define OW_TEST_CS_OS_DA 67    /* [3] half-band decimator, branch A */
+#define OW_TEST_CS_OS_DB 70    /* [3] branch B */
+#define OW_TEST_CS_OS_DD 73    /* down_delay */
+#define OW_TEST_CS_SPK_HPF 74  /* [7] b0 b1 b2 a1 a2 s1 s2 */
+#define OW_TEST_CS_SPK_LPF 81  /* [7] */
+#define OW_TEST_CS_SPK_CHAR 88
+#define OW_TEST_CS_SPK_A2 89
+#define OW_TEST_CS_SPK_A3 90
+#define OW_TEST_CS_SPK_TC 91
+#define OW_TEST_CS_SPK_TS 92
+#define OW_TEST_CS_FLAGS 93    /* u64, bit 0: the output guard fired, preamp and upsampler reset pending */
+#define OW_TEST_CS_COUNT 137
+int ow_test_engine_read_chain_rows(ow_engine*, int first_row, int n_rows, double* out);
+int ow_test_engine_write_chain_rows(ow_engine*, int first_row, int n_rows, const double* in);
+
 /* Plain device-to-host copy, for reading a block that ow_pool_render(pool, NULL, ...) left in HBM (ow_pool_device_output). */
 int ow_test_device_read(void* dst_host, const void* src_device, size_t bytes, int device);
 /* Plain host-to-device copy into a buffer of ow_device_alloc, for handing given audio to an entry point's audio_is_device path. */

@@ -217,6 +217,34 @@ int ow_test_engine_read_preamp_state(ow_engine* e, int shadow, double* out14) {
     }
     return 0;
 }
+// Rows [first_row, first_row + n_rows) of engine e's chain state, cs[(first_row + i) * I + e], copied out / in as they stand: the whole
+// output stage lives in rows CS_SM_SPK .. CS_SM_VOL, CS_OS_DA .. CS_SPK_TS and CS_FLAGS, so a test can start it from any state and read
+// what a block left behind.  The write is a state change behind the scheduler's back, like ow_test_pool_set_switch.
+static_assert(CS_SM_SPK == OW_TEST_CS_SM_SPK && CS_SM_VOL == OW_TEST_CS_SM_VOL && CS_OS_DA == OW_TEST_CS_OS_DA && CS_OS_DB == OW_TEST_CS_OS_DB &&
+              CS_OS_DD == OW_TEST_CS_OS_DD && CS_SPK_HPF == OW_TEST_CS_SPK_HPF && CS_SPK_LPF == OW_TEST_CS_SPK_LPF &&
+              CS_SPK_CHAR == OW_TEST_CS_SPK_CHAR && CS_SPK_A2 == OW_TEST_CS_SPK_A2 && CS_SPK_A3 == OW_TEST_CS_SPK_A3 &&
+              CS_SPK_TC == OW_TEST_CS_SPK_TC && CS_SPK_TS == OW_TEST_CS_SPK_TS && CS_FLAGS == OW_TEST_CS_FLAGS && CS_COUNT == OW_TEST_CS_COUNT,
+              "openwurli_hip_test.h names the output stage's chain-state rows by index");
+int ow_test_engine_read_chain_rows(ow_engine* e, int first_row, int n_rows, double* out) {
+    if (!e || !e->pool || !out || first_row < 0 || n_rows < 0 || first_row > CS_COUNT - n_rows) return -1;
+    ow_pool* p = e->pool;
+    if (!p->d_cs) return -1;
+    if (n_rows == 0) return 0;
+    if (hipSetDevice(p->device) != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess) return -1;
+    const double* src = p->d_cs + (size_t)first_row * p->I + e->index;
+    return hipMemcpy2D(out, sizeof(double), src, sizeof(double) * p->I, sizeof(double), (size_t)n_rows, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+int ow_test_engine_write_chain_rows(ow_engine* e, int first_row, int n_rows, const double* in) {
+    if (!e || !e->pool || !in || first_row < 0 || n_rows < 0 || first_row > CS_COUNT - n_rows) return -1;
+    ow_pool* p = e->pool;
+    if (!p->d_cs) return -1;
+    if (hipSetDevice(p->device) != hipSuccess) return -1;
+    invalidate_spec(p);                                   // a pending block-ahead result was produced from the old rows
+    if (hipStreamSynchronize(p->stream) != hipSuccess) return -1;
+    if (n_rows == 0) return 0;
+    double* dst = p->d_cs + (size_t)first_row * p->I + e->index;
+    return hipMemcpy2D(dst, sizeof(double) * p->I, in, sizeof(double), sizeof(double), (size_t)n_rows, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
 // plain device-to-host copy (tests read blocks that a render left in HBM: ow_pool_device_output)
 int ow_test_device_read(void* dst_host, const void* src_device, size_t bytes, int device) {
     if (!dst_host || !src_device) return -1;

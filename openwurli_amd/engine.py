@@ -91,6 +91,21 @@ class _EngineHandle:
             raise RuntimeError("ow_test_engine_read_preamp_state failed")
         return out
 
+    def read_chain_rows(self, first_row, n_rows):
+        """Test hook (openwurli_hip_test.h): rows [first_row, first_row + n_rows) of this engine's chain state as they stand, float64
+        (u64 rows as their bits)."""
+        out = np.zeros(int(n_rows), dtype=np.float64)
+        if self._lib.ow_test_engine_read_chain_rows(self._h, int(first_row), int(n_rows), out.ctypes.data) != 0:
+            raise RuntimeError("ow_test_engine_read_chain_rows failed")
+        return out
+
+    def write_chain_rows(self, first_row, rows):
+        """Test hook (openwurli_hip_test.h): overwrite rows [first_row, first_row + len(rows)) of this engine's chain state before the
+        next block."""
+        a = np.ascontiguousarray(rows, dtype=np.float64)
+        if self._lib.ow_test_engine_write_chain_rows(self._h, int(first_row), int(a.size), a.ctypes.data) != 0:
+            raise RuntimeError("ow_test_engine_write_chain_rows failed")
+
     def reset(self):
         self._lib.ow_engine_reset(self._h)
         binding.raise_if_error(self._lib)

@@ -41,7 +41,7 @@ struct Oversampler {
         for (size_t i = 0; i < n; ++i) {
             const double a = branch(OS_BRANCH_A, da, in[2 * i]);
             const double b = branch(OS_BRANCH_B, db, in[2 * i + 1]);
-            out[i] = (a + down_delay) * 0.5;
+            out[i] = (a + (stage_tweak().mutant == SM_NO_DOWN_DELAY ? b : down_delay)) * 0.5;
             down_delay = b;
         }
     }
@@ -343,19 +343,22 @@ struct PowerAmp {  // power_amp.rs:168-240
     inline void forward_path(double v, double& f_val, double& f_deriv) const {
         const double v_sq = v * v;
         const double vt_sq = CROSSOVER_VT * CROSSOVER_VT;
-        const double exp_term = std::exp(-v_sq / vt_sq);
+        const double exp_term = stage_lib(SL_EXP, std::exp(-v_sq / vt_sq));
         const double q = QUIESCENT_GAIN;
         const double cross_gain = q + (1.0 - q) * (1.0 - exp_term);
         const double v_cross = v * cross_gain;
         const double dcross_dv = cross_gain + v * (1.0 - q) * (2.0 * v / vt_sq) * exp_term;
         const double tanh_arg = v_cross / HEADROOM;
-        const double tanh_val = std::tanh(tanh_arg);
+        const double tanh_val = stage_lib(SL_TANH, std::tanh(tanh_arg));
         f_val = HEADROOM * tanh_val;
         f_deriv = (1.0 - tanh_val * tanh_val) * dcross_dv;
     }
     double process(double input) const {
         double y = rclamp(input * closed_loop_gain, -HEADROOM + NR_TOL, HEADROOM - NR_TOL);
-        for (int it = 0; it < 8; ++it) {
+        StageTweak& tw = stage_tweak();
+        const int max_sweeps = tw.mutant == SM_NEWTON_7 ? 7 : 8;
+        tw.tap_sweeps = 0; tw.tap_converged = 0;
+        for (int it = 0; it < max_sweeps; ++it) {
             const double error = input - feedback_beta * y;
             const double v = OPEN_LOOP_GAIN * error;
             double f_val, f_deriv;
@@ -364,7 +367,8 @@ struct PowerAmp {  // power_amp.rs:168-240
             const double jacobian = 1.0 + OPEN_LOOP_GAIN * feedback_beta * f_deriv;
             const double delta = residual / jacobian;
             y -= delta;
-            if (std::fabs(delta) < NR_TOL) break;
+            tw.tap_sweeps = it + 1;
+            if (std::fabs(delta) < NR_TOL) { tw.tap_converged = 1; break; }
         }
         return y / HEADROOM;
     }
@@ -386,12 +390,13 @@ struct Speaker {  // speaker.rs:50-139
     }
     void set_character(double ch) {
         const double c = rclamp(ch, 0.0, 1.0);
+        stage_tweak().tap_requested = c;
         if (std::fabs(c - character) > 0.002) { character = c; update_coefficients(); }
     }
     void update_coefficients() {
         const double c = character;
-        const double hpf_hz = 20.0 * std::pow(30.0 / 20.0, c);
-        const double lpf_hz = 20000.0 * std::pow(5500.0 / 20000.0, c);
+        const double hpf_hz = 20.0 * stage_lib(SL_POW, std::pow(30.0 / 20.0, c));
+        const double lpf_hz = 20000.0 * stage_lib(SL_POW, std::pow(5500.0 / 20000.0, c));
         hpf.set(Biquad::HIGHPASS, hpf_hz, 0.75, sample_rate);
         lpf.set(Biquad::LOWPASS, lpf_hz, 0.707, sample_rate);
         a2 = 0.2 * c;
@@ -402,10 +407,13 @@ struct Speaker {  // speaker.rs:50-139
         const double x2 = input * input;
         const double x3 = x2 * input;
         const double shaped = (input + a2 * x2 + a3 * x3) / (1.0 + a2 + a3);
-        const double limited = character < 0.001 ? shaped : std::tanh(shaped);
+        const StageTweak& tw = stage_tweak();
+        const double bypass_on = tw.mutant == SM_BYPASS_ON_SMOOTHER ? tw.tap_requested : character;
+        const double limited = bypass_on < 0.001 ? shaped : stage_lib(SL_TANH, std::tanh(shaped));
         const double power = x2;
-        thermal_state += (power - thermal_state) * thermal_alpha;
+        if (tw.mutant != SM_THERMAL_AFTER_GAIN) thermal_state += (power - thermal_state) * thermal_alpha;
         const double thermal_gain = 1.0 / (1.0 + thermal_coeff * std::sqrt(thermal_state));
+        if (tw.mutant == SM_THERMAL_AFTER_GAIN) thermal_state += (power - thermal_state) * thermal_alpha;
         const double filtered = hpf.process(limited * thermal_gain);
         return lpf.process(filtered);
     }

@@ -598,6 +598,114 @@ void owo_speaker_run(double sr, double character, double* x, size_t n) {
     for (size_t i = 0; i < n; ++i) x[i] = s.process(x[i]);
 }
 void owo_oversampler_down(const double* up, double* y, size_t n_out) { Oversampler os; os.downsample_2x(up, y, n_out); }
+
+// ---- the output stage as a function of its state rows (tests/post_stage_cases.py) ----
+// Row indices = the product's chain-state rows CS_* (openwurli_amd/csrc/ow_types.h; include/openwurli_hip_test.h names them): the two
+// smoothers' current / target / step / remaining (u64 bits), the half-band decimator, the speaker's biquads, character, a2, a3,
+// thermal coefficient and state, and the flags word (bit 0: the guard fired in this block).
+enum { SR_SM_SPK = 22, SR_SM_VOL = 26, SR_OS_DA = 67, SR_OS_DB = 70, SR_OS_DD = 73, SR_SPK_HPF = 74, SR_SPK_LPF = 81, SR_SPK_CHAR = 88,
+       SR_SPK_A2 = 89, SR_SPK_A3 = 90, SR_SPK_TC = 91, SR_SPK_TS = 92, SR_FLAGS = 93, SR_COUNT = 137 };
+static double sr_bits(uint64_t u) { double d; std::memcpy(&d, &u, 8); return d; }
+static uint64_t sr_u64(double d) { uint64_t u; std::memcpy(&u, &d, 8); return u; }
+static void sr_load_smoother(LinearSmoother& s, const double* rows, int f, uint32_t ramp) {
+    s.current = rows[f]; s.target = rows[f + 1]; s.step = rows[f + 2]; s.samples_remaining = (uint32_t)sr_u64(rows[f + 3]); s.ramp_samples = ramp;
+}
+static void sr_store_smoother(const LinearSmoother& s, double* rows, int f) {
+    rows[f] = s.current; rows[f + 1] = s.target; rows[f + 2] = s.step; rows[f + 3] = sr_bits((uint64_t)s.samples_remaining);
+}
+static void sr_load_biquad(Biquad& b, const double* r) { b.b0 = r[0]; b.b1 = r[1]; b.b2 = r[2]; b.a1 = r[3]; b.a2 = r[4]; b.s1 = r[5]; b.s2 = r[6]; }
+static void sr_store_biquad(const Biquad& b, double* r) { r[0] = b.b0; r[1] = b.b1; r[2] = b.b2; r[3] = b.a1; r[4] = b.a2; r[5] = b.s1; r[6] = b.s2; }
+static void sr_load_stage(const double* rows, Oversampler& os, Speaker& spk, LinearSmoother& sc, LinearSmoother& vol, uint32_t ramp) {
+    for (int i = 0; i < 3; ++i) { os.da[i] = rows[SR_OS_DA + i]; os.db[i] = rows[SR_OS_DB + i]; }
+    os.down_delay = rows[SR_OS_DD];
+    sr_load_biquad(spk.hpf, rows + SR_SPK_HPF); sr_load_biquad(spk.lpf, rows + SR_SPK_LPF);
+    spk.character = rows[SR_SPK_CHAR]; spk.a2 = rows[SR_SPK_A2]; spk.a3 = rows[SR_SPK_A3]; spk.thermal_coeff = rows[SR_SPK_TC]; spk.thermal_state = rows[SR_SPK_TS];
+    sr_load_smoother(sc, rows, SR_SM_SPK, ramp); sr_load_smoother(vol, rows, SR_SM_VOL, ramp);
+}
+static void sr_store_stage(double* rows, const Oversampler& os, const Speaker& spk, const LinearSmoother& sc, const LinearSmoother& vol) {
+    for (int i = 0; i < 3; ++i) { rows[SR_OS_DA + i] = os.da[i]; rows[SR_OS_DB + i] = os.db[i]; }
+    rows[SR_OS_DD] = os.down_delay;
+    sr_store_biquad(spk.hpf, rows + SR_SPK_HPF); sr_store_biquad(spk.lpf, rows + SR_SPK_LPF);
+    rows[SR_SPK_CHAR] = spk.character; rows[SR_SPK_A2] = spk.a2; rows[SR_SPK_A3] = spk.a3; rows[SR_SPK_TC] = spk.thermal_coeff; rows[SR_SPK_TS] = spk.thermal_state;
+    sr_store_smoother(sc, rows, SR_SM_SPK); sr_store_smoother(vol, rows, SR_SM_VOL);
+}
+// An engine's output-stage rows out of / into the engine (rows[SR_COUNT]; rows outside the stage are left alone).  The flags word reads 0:
+// the engine resets preamp and upsampler on the spot.
+void owo_engine_stage_rows(void* e, double* rows) {
+    WurliEngine* w = (WurliEngine*)e;
+    sr_store_stage(rows, w->oversampler, w->speaker, w->speaker_character, w->volume);
+    rows[SR_FLAGS] = sr_bits(0);
+}
+void owo_engine_set_stage_rows(void* e, const double* rows) {
+    WurliEngine* w = (WurliEngine*)e;
+    sr_load_stage(rows, w->oversampler, w->speaker, w->speaker_character, w->volume, w->volume.ramp_samples);
+}
+// One block of the output stage in the order of WurliEngine::render (engine.rs:425-460): the whole block through the power amp
+// (amp_kind 0: the behavioural amp on tap x FIXED_CIRCUIT_DRIVE; 1: identity, the tap is the melange amp's output already) and
+// downsample_2x (osr 2) first, then per host sample smoother -> set_character -> Speaker::process -> gain x volume -> f32 -> guard.  The
+// guard's oversampler.reset() therefore acts on the post-block decimator; its preamp / upsampler / melange-amp resets are outside the
+// stage and show as bit 0 of the flags row.  set_flags bit 1 / bit 2: set_speaker_character(spk_target) / set_volume(vol_target) in
+// front of the block.  tap[n * osr]; info int32: [n * osr] Newton sweeps, [n * osr] converged, [n] character redesigned, [n] guard fired.
+// perturb (or NULL): ulps of exp, tanh, pow, cos, sin, then the pattern (SP_*) and a seed.  mutant: SM_*.  out_f64 (or NULL): the sample in
+// front of the f32 cast, which the comparison needs to tell a rounding midpoint.  Returns 0, <0 on a bad argument.
+int owo_output_stage_block(double host_rate, int osr, int amp_kind, const double* rows_in, unsigned set_flags, double spk_target, double vol_target,
+                           const double* tap, size_t n, double* rows_out, float* out_f32, int* info, const int* perturb, int mutant, double* out_f64) {
+    if (!(host_rate > 0.0) || (osr != 1 && osr != 2) || (amp_kind != 0 && amp_kind != 1) || !rows_in || !tap || !rows_out || !out_f32 || !info || n == 0) return -1;
+    if (mutant < SM_NONE || mutant > SM_NEWTON_7) return -1;
+    StageTweak& tw = stage_tweak();
+    tw = StageTweak{};
+    Oversampler os;
+    PowerAmp pa;
+    Speaker spk;
+    spk.init(host_rate);                 // sample_rate, thermal_alpha; everything else comes from the rows
+    LinearSmoother sc, vol;
+    sr_load_stage(rows_in, os, spk, sc, vol, ramp_samples_for_rate(host_rate));
+    if (perturb) {
+        for (int i = 0; i < SL_COUNT; ++i) tw.ulp[i] = perturb[i];
+        tw.pattern = perturb[SL_COUNT];
+        tw.rng = 0x9E3779B97F4A7C15ull ^ ((uint64_t)(uint32_t)perturb[SL_COUNT + 1] * 0xD1342543DE82EF95ull);
+        if (tw.rng == 0) tw.rng = 1;
+    }
+    tw.mutant = mutant;
+    if (mutant == SM_THERMAL_ALPHA_CHAIN_RATE) spk.thermal_alpha = 1.0 / (5.0 * host_rate * (double)osr);
+    if (set_flags & 2u) sc.set_target(spk_target);
+    if (set_flags & 4u) vol.set_target(vol_target);
+    const size_t n_os = n * (size_t)osr;
+    int* sweeps = info; int* converged = info + n_os; int* redesigned = info + 2 * n_os; int* fired = info + 2 * n_os + n;
+    std::vector<double> up(n_os), down(n);
+    for (size_t i = 0; i < n_os; ++i) {
+        if (amp_kind == 0) { up[i] = pa.process(tap[i] * FIXED_CIRCUIT_DRIVE); sweeps[i] = tw.tap_sweeps; converged[i] = tw.tap_converged; }
+        else { up[i] = tap[i]; sweeps[i] = 0; converged[i] = 1; }
+    }
+    if (osr == 2) os.downsample_2x(up.data(), down.data(), n);
+    else down = up;
+    bool any_fired = false;
+    for (size_t i = 0; i < n; ++i) {
+        const double before = spk.character;
+        spk.set_character(sc.next());
+        redesigned[i] = spk.character != before;
+        const double shaped = spk.process(down[i]);
+        const double post_gain = shaped * POST_SPEAKER_GAIN * vol.next();
+        const float sample = (float)post_gain;
+        if (out_f64) out_f64[i] = post_gain;
+        const bool ok = mutant == SM_GUARD_ON_F64 ? std::isfinite(post_gain) : std::isfinite(sample);
+        fired[i] = !ok;
+        if (ok) out_f32[i] = sample;
+        else {
+            const double ts = spk.thermal_state;
+            os.reset();
+            spk.reset();
+            if (mutant == SM_GUARD_KEEPS_TS) spk.thermal_state = ts;
+            out_f32[i] = 0.0f;
+            any_fired = true;
+        }
+    }
+    std::memcpy(rows_out, rows_in, sizeof(double) * SR_COUNT);
+    sr_store_stage(rows_out, os, spk, sc, vol);
+    rows_out[SR_FLAGS] = sr_bits((sr_u64(rows_in[SR_FLAGS]) & ~1ull) | (any_fired ? 1ull : 0ull));
+    tw = StageTweak{};
+    return 0;
+}
 // G (without R_ldr), 2w and v at the DC point of the legacy preamp, for the layer-1 / layer-4 tests of the reference's pyramid
 void owo_preamp_gw(double sr, double* g64, double* two_w8) {
     DkPreamp p;

@@ -26,6 +26,41 @@ namespace owo {
 constexpr double PI_ = 3.14159265358979323846;   // std::f64::consts::PI
 constexpr double TAU_ = 6.28318530717958647692;  // std::f64::consts::TAU
 
+// ------------------------------------------------ instrumentation of the output stage (owo_output_stage_block, ow_oracle_capi.cpp)
+// Off (all zero) everywhere else.  The stage's library calls -- exp / tanh of the behavioural power amp, tanh / pow of the speaker, cos /
+// sin of its biquad designs -- return through stage_lib(), which moves the result by ulp[fn] doubles in the direction `pattern` gives:
+// what another libm may do to it.  `mutant` selects one deliberately wrong variant of the stage (tests/test_oracle_post_stage_cases.py
+// checks that the comparison sees each); the taps report what the last PowerAmp::process / Speaker::set_character did.
+enum { SL_EXP = 0, SL_TANH = 1, SL_POW = 2, SL_COS = 3, SL_SIN = 4, SL_COUNT = 5 };
+enum { SP_OFF = 0, SP_UP = 1, SP_DOWN = 2, SP_ALTERNATE = 3, SP_RANDOM = 4 };
+enum { SM_NONE = 0, SM_NO_DOWN_DELAY = 1, SM_THERMAL_AFTER_GAIN = 2, SM_BYPASS_ON_SMOOTHER = 3, SM_THERMAL_ALPHA_CHAIN_RATE = 4,
+       SM_GUARD_KEEPS_TS = 5, SM_GUARD_ON_F64 = 6, SM_NEWTON_7 = 7 };
+struct StageTweak {
+    int ulp[SL_COUNT];
+    int pattern, mutant;
+    uint64_t rng, calls;
+    int tap_sweeps, tap_converged;   // PowerAmp::process: Newton sweeps made, |delta| < NR_TOL reached
+    double tap_requested;            // Speaker::set_character: the clamped value it was called with
+};
+inline StageTweak& stage_tweak() { static thread_local StageTweak t = {}; return t; }
+inline double stage_lib(int fn, double v) {
+    StageTweak& t = stage_tweak();
+    if (t.pattern == SP_OFF || t.ulp[fn] == 0 || !std::isfinite(v) || v == 0.0) return v;   // (tanh(0), sin(0), an underflown exp: exact in any libm)
+    bool up;
+    switch (t.pattern) {
+        case SP_UP: up = true; break;
+        case SP_DOWN: up = false; break;
+        case SP_ALTERNATE: up = (t.calls & 1u) == 0u; break;
+        default: t.rng ^= t.rng << 13; t.rng ^= t.rng >> 7; t.rng ^= t.rng << 17; up = (t.rng >> 33) & 1u; break;   // xorshift64
+    }
+    t.calls += 1;
+    double r = v;
+    for (int i = 0; i < t.ulp[fn]; ++i) r = std::nextafter(r, up ? INFINITY : -INFINITY);
+    // a library keeps its function's range: exp >= 0, |tanh|, |cos|, |sin| <= 1
+    if (fn == SL_EXP ? r < 0.0 : (fn != SL_POW && std::fabs(r) > 1.0)) return v;
+    return r;
+}
+
 // ---------------------------------------------------------------- filters.rs
 struct Biquad {
     double b0 = 1, b1 = 0, b2 = 0, a1 = 0, a2 = 0;
@@ -33,7 +68,7 @@ struct Biquad {
     enum Kind { LOWPASS, HIGHPASS, BANDPASS };
     void set(Kind kind, double fc, double q, double sr) {  // RBJ cookbook; keeps state (filters.rs:39-49)
         const double w0 = 2.0 * PI_ * fc / sr;
-        const double cw = std::cos(w0), sw = std::sin(w0);
+        const double cw = stage_lib(SL_COS, std::cos(w0)), sw = stage_lib(SL_SIN, std::sin(w0));
         const double alpha = sw / (2.0 * q);
         const double a0 = 1.0 + alpha;
         double nb0, nb1, nb2;

@@ -88,9 +88,13 @@ def pa_engine_setup(k):
     """(notes, velocity, volume) of engine k.  Engine 0 is silent.  Engines 1..31 are struck before the warm-up block: from one soft
     key to the whole bench chord at ff, so the preamp tap runs from microvolts into the preamp's clipping.  Engines 32..63 are struck
     right before the first recorded block: their taps grow from zero through the microvolt range, where the power amp's crossover term
-    (|A error| near 0.013 V) makes its Newton loop take most sweeps.  The loudest chord leaves about 0.4 V at the tap (the volume acts
+    (|A error| near 0.013 V) takes its Newton loop from one sweep to two, three and four (the oracle's `info`, owo_output_stage_block: two
+    from 1.8e-6 V, three from 1.3e-5 V, four from 2.9e-5 V).  The loop takes MOST sweeps -- five to eight -- only for |tap| in
+    1.0512 .. 1.2864 V, where the closed-loop estimate meets the +-22 V rail; the engines here cross that band only in passing
+    (tests/post_stage_cases.py places kicks inside it).  The loudest chord leaves about 0.4 V at the tap (the volume acts
     behind the power amp), so the volts come from PA_KICKS: a finite kick of the preamp's output node before the first recorded block
-    (the hook of tests/test_gpu_preamp_pair.py::test_preamp_pair_finite_kicks), which the tap carries for the next samples."""
+    (the hook of tests/test_gpu_preamp_pair.py::test_preamp_pair_finite_kicks), which the tap carries, alternating in sign, for the
+    blocks that follow: 0.5, 1, 2 and 4 V alone take three, four, two and two sweeps."""
     if k == 0:
         return [], 0.0, 0.5
     j = (k - 1) % 31                       # 0..30 in both halves

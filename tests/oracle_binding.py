@@ -170,6 +170,17 @@ class OracleEngine:
 
     def poke_power_amp_node(self, node, volts): self.L.owo_engine_poke_pa_node(self.h, int(node), C.c_double(volts))
 
+    def stage_rows(self):
+        """the output stage's state as the product's chain-state rows (float64 [STAGE_ROW_COUNT], CS_* indices; the rest 0)"""
+        rows = np.zeros(STAGE_ROW_COUNT)
+        self.L.owo_engine_stage_rows(self.h, _p(rows))
+        return rows
+
+    def set_stage_rows(self, rows):
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        assert rows.shape == (STAGE_ROW_COUNT,)
+        self.L.owo_engine_set_stage_rows(self.h, _p(rows))
+
     def count_voices_in_state(self, st): return self.L.owo_engine_count_state(self.h, int(st))
     def active_voice_count(self): return self.L.owo_engine_active_voice_count(self.h)
     def steal_voice_count(self): return self.L.owo_engine_steal_voice_count(self.h)
@@ -179,6 +190,47 @@ class OracleEngine:
 
 
 DK_EXIT_CONVERGED, DK_EXIT_SINGULAR, DK_EXIT_SIX_UPDATES = 0, 1, 2
+
+# ---- the output stage as a function of its state rows (owo_output_stage_block; tests/post_stage_cases.py)
+STAGE_ROW_COUNT = 137            # CS_COUNT of openwurli_amd/csrc/ow_types.h: rows are indexed as the product's chain state is
+STAGE_AMP_BEHAVIORAL, STAGE_AMP_IDENTITY = 0, 1
+STAGE_MUTANTS = {"none": 0, "no_down_delay": 1, "thermal_after_gain": 2, "bypass_on_smoother": 3, "thermal_alpha_chain_rate": 4,
+                 "guard_keeps_ts": 5, "guard_on_f64": 6, "newton_7": 7}
+STAGE_PATTERNS = {"up": 1, "down": 2, "alternate": 3, "random": 4}
+# How far a library result of the stage is moved, in doubles: the device function's documented bound plus glibc's.
+#   exp    1 + 1   exp_any is the device library's f64 exp operation for operation (ow_chain_dev.h; within 1 ulp of the true value on the
+#                  yardstick of tests/test_gpu_division.py); glibc's exp 1
+#   tanh   2 + 2   tanh_fast <= 2 ulp (DESIGN section 2 deviation 14, test_gpu_division.py); glibc's tanh 2
+#   pow    2 + 2   the device library's pow and glibc's, "a 2-ulp function on each side" (the isolation score's rows)
+#   cos    2 + 2   "a sin / cos good to 2 ulp on both sides" (DESIGN, the note audits' bars)
+#   sin    2 + 2
+# Division and sqrt are IEEE on both sides (ow_div is tested bit-equal to the division) and are left alone.
+STAGE_PERTURB_ULPS = (2, 4, 4, 4, 4)
+
+
+def output_stage_block(host_rate, rows_in, tap, n, set_flags=0, spk_target=0.0, vol_target=0.0, amp_kind=STAGE_AMP_BEHAVIORAL, pattern=None,
+                       seed=0, mutant="none", ulps=STAGE_PERTURB_ULPS):
+    """One block of n host samples of the oracle's output stage from the state rows `rows_in` [STAGE_ROW_COUNT] and the stage's input
+    `tap` [n * osr] (osr = 2 below 88.2 kHz): the preamp tap with the behavioural amp, the amp's output with STAGE_AMP_IDENTITY.
+    set_flags bit 1 / 2: set_speaker_character(spk_target) / set_volume(vol_target) in front of the block.  pattern: None or a key of
+    STAGE_PATTERNS -- every exp / tanh / pow / cos / sin result `ulps` doubles away, that way.  Returns (rows_out, out float32 [n], info)
+    with info = dict(sweeps [n * osr], converged [n * osr], redesigned [n], fired [n], out64 [n]: the sample in front of the f32 cast)."""
+    n = int(n)
+    osr = 2 if host_rate < 88200.0 else 1
+    rows_in = np.ascontiguousarray(rows_in, dtype=np.float64)
+    tap = np.ascontiguousarray(tap, dtype=np.float64)
+    assert rows_in.shape == (STAGE_ROW_COUNT,) and tap.shape == (n * osr,), (rows_in.shape, tap.shape, n, osr)
+    rows_out = np.zeros(STAGE_ROW_COUNT); out = np.zeros(n, dtype=np.float32); info = np.zeros(2 * n * osr + 2 * n, dtype=np.int32)
+    out64 = np.zeros(n)
+    pert = None
+    if pattern is not None:
+        pert = np.array(list(ulps) + [STAGE_PATTERNS[pattern], int(seed)], dtype=np.int32)
+    rc = lib().owo_output_stage_block(C.c_double(host_rate), osr, int(amp_kind), _p(rows_in), C.c_uint(int(set_flags)), C.c_double(spk_target),
+                                      C.c_double(vol_target), _p(tap), C.c_size_t(n), _p(rows_out), _p(out), _p(info),
+                                      None if pert is None else _p(pert), int(STAGE_MUTANTS[mutant]), _p(out64))
+    assert rc == 0, rc
+    m = n * osr
+    return rows_out, out, dict(sweeps=info[:m], converged=info[m:2 * m], redesigned=info[2 * m:2 * m + n], fired=info[2 * m + n:], out64=out64)
 
 
 def dk_step_cases(rate, states, inputs, g_ldr, g_ldr_prev, perturbed=False):

@@ -4,7 +4,11 @@ written as three-address fused multiply-adds (fma3), so every argument has to gi
 64 engines x 129 samples x 2 chain samples = 16 512 inputs of the power amp per case, with post_pair 0 (k_post<true>) and 1
 (k_post<false, true>): a silent engine, taps from below a microvolt up to +-4 V (chords of 1..64 keys from pp to ff; volts by a finite
 kick of the preamp's output node), and engines struck right before the recorded blocks, whose taps grow from zero through the crossover
-region (|A error| near 0.013 V) where the Newton loop takes most sweeps."""
+region (|A error| near 0.013 V), where the Newton loop goes from one sweep to two, three and four.  Most sweeps are taken elsewhere:
+the oracle's `info` (owo_output_stage_block, tests/post_stage_cases.py) finds five to eight only for |tap| in 1.0512 .. 1.2864 V,
+where the closed-loop estimate meets the +-22 V rail (eight in 1.27472 .. 1.27707 V).  A kick leaves the tap at -kick, +kick, ... for
+the block, so the kicks here (0.5, 1, 2, 4 V: alone three, four, two and two sweeps) enter that band only where the engine's chord carries
+a 1 V kick into it for a few samples; tests/test_gpu_post_stage.py places kicks inside it and compares with the oracle in f64."""
 import os
 
 import numpy as np
