@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import BARK_ROW_FIELDS, OwBarkCfg, OwBarkRow, OwError, load_library, take_error
+from .binding import BARK_ROW_FIELDS, OwBarkCfg, OwBarkRow, OwError, check, load_library, take_error  # noqa: F401
 from .intermod_audit import NOTE_JOB_DTYPE, note_jobs
 from ._rust_text import _f, midi_note_name, parse_csv_u8, samples  # noqa: F401
 
@@ -23,9 +23,7 @@ KIND_NAMES = ("legacy", "melange")
 ML_VELOCITIES = (20, 35, 50, 65, 80, 95, 110, 127)          # the velocity layers of the other grids
 
 # numpy view of include/openwurli_hip.h ow_bark_row
-ROW_DTYPE = np.dtype([("note", "u1"), ("velocity", "u1"), ("reserved", "u1", (6,)), ("window_start", "<u4"), ("window_end", "<u4")] +
-                     [(f, "<f8") for f in BARK_ROW_FIELDS])
-assert ROW_DTYPE.itemsize == C.sizeof(OwBarkRow)
+ROW_DTYPE = np.dtype(OwBarkRow)
 
 
 def run_jobs(jobs, preamp_kind=PREAMP_LEGACY8, duration=DURATION, measure_start=MEASURE_START, device=0, taps=False):
@@ -36,10 +34,8 @@ def run_jobs(jobs, preamp_kind=PREAMP_LEGACY8, duration=DURATION, measure_start=
     rows = np.zeros(jb.size, dtype=ROW_DTYPE)
     n = samples(duration)
     tp = np.zeros((jb.size, 3, n)) if taps else None
-    rc = L.ow_bark_audit(jb.ctypes.data_as(C.c_void_p), jb.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
-                         tp.ctypes.data_as(C.c_void_p) if taps else None, n)
-    if rc < 0:
-        raise OwError(take_error(L))
+    check(L, L.ow_bark_audit(jb.ctypes.data_as(C.c_void_p), jb.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
+                             tp.ctypes.data_as(C.c_void_p) if taps else None, n))
     return (rows, tp) if taps else rows
 
 

@@ -2,6 +2,8 @@
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
@@ -50,8 +52,7 @@ class OwMlpTrainModel(C.Structure):
                 ("epochs", C.c_uint32), ("patience", C.c_uint32), ("sched_patience", C.c_uint32), ("target_mask", C.c_uint32)]
 
 
-MLP_TRAIN_MODEL_DTYPE = [("lr", "<f8"), ("min_lr", "<f8"), ("weight_decay", "<f8"), ("huber_delta", "<f8"), ("sched_factor", "<f8"),
-                         ("epochs", "<u4"), ("patience", "<u4"), ("sched_patience", "<u4"), ("target_mask", "<u4")]
+MLP_TRAIN_MODEL_DTYPE = np.dtype(OwMlpTrainModel)
 MLP_TRAIN_MAX_ROW_EPOCHS = 1 << 26      # include/openwurli_hip.h OW_MLP_TRAIN_MAX_ROW_EPOCHS
 
 
@@ -68,15 +69,14 @@ class OwMlpTrainResult(C.Structure):
                 ("best_epoch", C.c_uint32), ("epochs_run", C.c_uint32), ("lr_reductions", C.c_uint32), ("status", C.c_uint32)]
 
 
-MLP_TRAIN_RESULT_DTYPE = [("best_val_loss", "<f8"), ("last_train_loss", "<f8"), ("last_val_loss", "<f8"), ("last_lr", "<f8"),
-                          ("best_epoch", "<u4"), ("epochs_run", "<u4"), ("lr_reductions", "<u4"), ("status", "<u4")]
+MLP_TRAIN_RESULT_DTYPE = np.dtype(OwMlpTrainResult)
 
 
 class OwMidiEvent(C.Structure):
     _fields_ = [("engine", C.c_uint32), ("type", C.c_uint8), ("note", C.c_uint8), ("reserved", C.c_uint16), ("value", C.c_float)]
 
 
-MIDI_DTYPE = [("engine", "<u4"), ("type", "u1"), ("note", "u1"), ("reserved", "<u2"), ("value", "<f4")]
+MIDI_DTYPE = np.dtype(OwMidiEvent)
 
 
 ABI_VERSION = 8      # include/openwurli_hip.h OW_ABI_VERSION; load_library() checks it against ow_abi_version()
@@ -91,8 +91,11 @@ class OwBatchCfg(C.Structure):
         super().__init__(C.sizeof(OwBatchCfg), C.sizeof(OwJob), sample_rate, duration_s, device, preamp_kind, power_amp_kind, no_rail_sag)
 
 
+AUDIT_HARMONICS = 12      # include/openwurli_hip.h OW_AUDIT_HARMONICS
+
+
 class OwAliasAuditResult(C.Structure):
-    _fields_ = [("f0_hz", C.c_double), ("h1_dbfs", C.c_double), ("harmonic_db", C.c_double * 12), ("harmonic_dbc", C.c_double * 12),
+    _fields_ = [("f0_hz", C.c_double), ("h1_dbfs", C.c_double), ("harmonic_db", C.c_double * AUDIT_HARMONICS), ("harmonic_dbc", C.c_double * AUDIT_HARMONICS),
                 ("max_step_up_db", C.c_double), ("max_step_up_from_harmonic", C.c_uint32), ("reserved", C.c_uint32),
                 ("hf_band_dbc", C.c_double)]
 
@@ -101,7 +104,7 @@ class OwTimedEvent(C.Structure):
     _fields_ = [("time_s", C.c_double), ("type", C.c_uint8), ("note", C.c_uint8), ("value", C.c_uint8), ("reserved", C.c_uint8 * 5)]
 
 
-TIMED_EVENT_DTYPE = [("time_s", "<f8"), ("type", "u1"), ("note", "u1"), ("value", "u1"), ("reserved", "u1", (5,))]
+TIMED_EVENT_DTYPE = np.dtype(OwTimedEvent)
 
 
 class OwMidiRenderCfg(C.Structure):
@@ -303,13 +306,11 @@ class OwPumpRow(C.Structure):
                [(f, C.c_uint64) for f in ("nr_exhausted", "be_fallbacks", "voltage_damps", "nan_resets")]
 
 
-# every symbol include/openwurli_hip.h declares: name -> (restype, argtypes)
-_VP = C.c_void_p
 class OwSegment(C.Structure):
     _fields_ = [("row", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("n_harmonics", C.c_uint32), ("f0", C.c_double)]
 
 
-SEGMENT_DTYPE = [("row", "<u4"), ("start", "<u4"), ("end", "<u4"), ("n_harmonics", "<u4"), ("f0", "<f8")]
+SEGMENT_DTYPE = np.dtype(OwSegment)
 MAX_HARMONICS = 8
 WAV_NONE, WAV_ROUND, WAV_TRUNCATE = -1, 0, 1
 GOERTZEL_OFFSETS = 11            # include/openwurli_hip.h OW_GOERTZEL_OFFSETS
@@ -321,7 +322,7 @@ class OwHarmonicsCfg(C.Structure):
                 ("wav24_mode", C.c_int), ("device", C.c_int), ("audio_is_device", C.c_int), ("reserved", C.c_int)]
 
     def __init__(self, sample_rate=44100.0, search_pct=0.01, wav24_mode=WAV_NONE, device=0, audio_is_device=0):
-        super().__init__(C.sizeof(OwHarmonicsCfg), 24, sample_rate, search_pct, wav24_mode, device, audio_is_device, 0)
+        super().__init__(C.sizeof(OwHarmonicsCfg), C.sizeof(OwSegment), sample_rate, search_pct, wav24_mode, device, audio_is_device, 0)
 
 
 class OwIsoNote(C.Structure):
@@ -329,8 +330,7 @@ class OwIsoNote(C.Structure):
                 ("window_end", C.c_double), ("id_key", C.c_int64), ("midi_note", C.c_int32), ("score", C.c_int32)]
 
 
-ISO_NOTE_DTYPE = [("onset_s", "<f8"), ("offset_s", "<f8"), ("amplitude", "<f8"), ("window_start", "<f8"), ("window_end", "<f8"),
-                  ("id_key", "<i8"), ("midi_note", "<i4"), ("score", "<i4")]
+ISO_NOTE_DTYPE = np.dtype(OwIsoNote)
 
 
 class OwIsoCfg(C.Structure):
@@ -342,6 +342,8 @@ class OwIsoCfg(C.Structure):
         super().__init__(C.sizeof(OwIsoCfg), C.sizeof(OwIsoNote), device, 0, collision_ratio, decay_rate, midi_freq, kernel_ms_out)
 
 
+# every symbol include/openwurli_hip.h declares: name -> (restype, argtypes)
+_VP = C.c_void_p
 SYMBOLS = {
     "ow_abi_version": (C.c_int, []),
     "ow_last_error": (C.c_char_p, []),
@@ -497,12 +499,19 @@ def load_library():
         raise OwError(f"{path} not found: build it with ./build.sh (hipcc --offload-arch=gfx950); "
                       "openwurli-hip has no CPU fallback")
     lib = C.CDLL(path)
+
+    def bind(name, res, args):
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise OwError(f"{path} does not export {name}: rebuild with ./build.sh")
+        fn.restype, fn.argtypes = res, args
+        return fn
+
+    built = bind("ow_abi_version", *SYMBOLS["ow_abi_version"])()      # before anything else: a stale library is named as such
+    if built != ABI_VERSION:
+        raise OwError(f"{path} was built against OW_ABI_VERSION {built}, this binding against {ABI_VERSION}: rebuild with ./build.sh")
     for name, (res, args) in list(SYMBOLS.items()) + list(TEST_SYMBOLS.items()):
-        fn = getattr(lib, name)  # AttributeError if the library does not export a declared symbol
-        fn.restype = res
-        fn.argtypes = args
-    if lib.ow_abi_version() != ABI_VERSION:
-        raise OwError(f"{path} was built against OW_ABI_VERSION {lib.ow_abi_version()}, this binding against {ABI_VERSION}: rebuild with ./build.sh")
+        bind(name, res, args)
     _LIB = lib
     return lib
 
@@ -519,6 +528,13 @@ def take_error(lib=None):
     msg = last_error(lib)
     lib.ow_clear_error()
     return msg
+
+
+def check(lib, rc):
+    """rc of an entry point that reports failure by a negative return: raises the recorded reason, else returns rc."""
+    if rc < 0:
+        raise OwError(take_error(lib))
+    return rc
 
 
 def raise_if_error(lib=None):

@@ -9,8 +9,8 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from .binding import (CALIB_SAMPLES, CALIBRATE_ROW_FIELDS, OwCalibPoint, OwCalibrateCfg, OwCalibrateRow, OwError, load_library,
-                      take_error)
+from .binding import (CALIB_SAMPLES, CALIBRATE_ROW_FIELDS, OwCalibPoint, OwCalibrateCfg, OwCalibrateRow, OwError, check,
+                      load_library, take_error)  # noqa: F401
 
 from ._rust_text import BASE_SR, midi_note_name  # noqa: F401
 MIDI_LO, MIDI_HI = 33, 96                                   # tables.rs:6-7
@@ -61,11 +61,8 @@ class CalibrateRow:                                         # main.rs:1099-1121
 
 
 # numpy views of the C structs (include/openwurli_hip.h ow_calib_point / ow_calibrate_row), for grids of 10^4..10^5 points
-POINT_DTYPE = np.dtype([("note", "u1"), ("velocity", "u1"), ("zero_trim", "u1"), ("reserved", "u1", (5,)),
-                        ("ds_at_c4", "<f8"), ("ds_exponent", "<f8"), ("ds_clamp_lo", "<f8"), ("ds_clamp_hi", "<f8"),
-                        ("target_db", "<f8"), ("voicing_slope", "<f8")])
-ROW_DTYPE = np.dtype([("midi", "u1"), ("velocity", "u1"), ("reserved", "u1", (6,))] + [(f, "<f8") for f in CALIBRATE_ROW_FIELDS])
-assert POINT_DTYPE.itemsize == C.sizeof(OwCalibPoint) and ROW_DTYPE.itemsize == C.sizeof(OwCalibrateRow)
+POINT_DTYPE = np.dtype(OwCalibPoint)
+ROW_DTYPE = np.dtype(OwCalibrateRow)
 
 
 def make_points(notes: Sequence[int], velocities: Sequence[int], cfgs: Sequence[CalibrationConfig]) -> np.ndarray:
@@ -100,10 +97,8 @@ def run_points(points: np.ndarray, volume: float, speaker_char: float, preamp_ki
     rows = np.zeros(pts.size, dtype=ROW_DTYPE)
     tp = np.zeros((pts.size, 5, CALIB_SAMPLES)) if taps else None
     cfg = OwCalibrateCfg(float(volume), float(speaker_char), int(device), int(preamp_kind), int(power_amp_kind))
-    rc = L.ow_calibrate(pts.ctypes.data_as(C.c_void_p), pts.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
-                        tp.ctypes.data_as(C.c_void_p) if tp is not None else None, CALIB_SAMPLES)
-    if rc != 0:
-        raise OwError(take_error(L))
+    check(L, L.ow_calibrate(pts.ctypes.data_as(C.c_void_p), pts.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
+                            tp.ctypes.data_as(C.c_void_p) if tp is not None else None, CALIB_SAMPLES))
     return (rows, tp) if taps else rows
 
 

@@ -15,20 +15,15 @@ from typing import Optional
 import numpy as np
 
 from .binding import (CENTROID_MAX_WINDOW, CENTROID_MISS, CENTROID_NO_DATA, CENTROID_OK, OwCentroidCfg, OwCentroidJob, OwCentroidRow, OwError,
-                      load_library, take_error)
+                      check, load_library, take_error)
 from ._rust_text import BASE_SR, _f, as_usize as _as_usize, midi_note_name, samples  # noqa: F401
 
 ML_VELOCITIES = (20, 35, 50, 65, 80, 95, 110, 127)          # the ML pipeline's velocity layers (ml/render_model_notes.py:26)
 STATUS = {CENTROID_NO_DATA: "", CENTROID_OK: "OK", CENTROID_MISS: "MISS"}
 
 # numpy views of include/openwurli_hip.h ow_centroid_job / ow_centroid_row
-JOB_DTYPE = np.dtype([("note", "u1"), ("velocity", "u1"), ("no_preamp", "u1"), ("no_poweramp", "u1"), ("has_displacement_scale", "u1"),
-                      ("reserved", "u1", (3,)), ("displacement_scale", "<f8"), ("volume", "<f8"), ("speaker", "<f8"), ("r_ldr", "<f8")])
-ROW_DTYPE = np.dtype([("c10", "<f8"), ("c300", "<f8"), ("drift", "<f8"), ("attack_lo", "<f8"), ("attack_hi", "<f8"), ("sustain_lo", "<f8"),
-                      ("sustain_hi", "<f8"), ("drift_lo", "<f8"), ("drift_hi", "<f8"), ("frame10", "<i4"), ("frame300", "<i4"),
-                      ("has_c10", "u1"), ("has_c300", "u1"), ("attack_status", "u1"), ("sustain_status", "u1"), ("drift_status", "u1"),
-                      ("reserved", "u1", (3,))])
-assert JOB_DTYPE.itemsize == C.sizeof(OwCentroidJob) and ROW_DTYPE.itemsize == C.sizeof(OwCentroidRow)
+JOB_DTYPE = np.dtype(OwCentroidJob)
+ROW_DTYPE = np.dtype(OwCentroidRow)
 
 
 def make_job(note=60, velocity=100, volume=0.60, speaker=1.0, ldr=1_000_000.0, no_preamp=False, no_poweramp=False,
@@ -88,10 +83,7 @@ def frame_count(duration=1.0, window_ms=5.0, hop_ms=2.5, end_ms=500.0, preamp_ki
     """``ow_centroid_frame_count`` (host only): raises OwError where the library refuses the configuration."""
     L = load_library()
     cfg = OwCentroidCfg(float(duration), float(window_ms), float(hop_ms), float(end_ms), 0, int(preamp_kind), int(power_amp_kind))
-    n = L.ow_centroid_frame_count(C.byref(cfg))
-    if n < 0:
-        raise OwError(take_error(L))
-    return int(n)
+    return int(check(L, L.ow_centroid_frame_count(C.byref(cfg))))
 
 
 def run_jobs(jobs, duration=1.0, window_ms=5.0, hop_ms=2.5, end_ms=500.0, device=0, audio=False, preamp_kind=0, power_amp_kind=0):
@@ -106,10 +98,8 @@ def run_jobs(jobs, duration=1.0, window_ms=5.0, hop_ms=2.5, end_ms=500.0, device
     frames = np.zeros((jb.size, nf))
     n = samples(duration)
     au = np.zeros((jb.size, n)) if audio else None
-    rc = L.ow_centroid_track(jb.ctypes.data_as(C.c_void_p), jb.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p), frames.ctypes.data_as(C.c_void_p), nf,
-                             au.ctypes.data_as(C.c_void_p) if audio else None, n)
-    if rc < 0:
-        raise OwError(take_error(L))
+    rc = check(L, L.ow_centroid_track(jb.ctypes.data_as(C.c_void_p), jb.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p), frames.ctypes.data_as(C.c_void_p),
+                                      nf, au.ctypes.data_as(C.c_void_p) if audio else None, n))
     assert rc == nf
     return (rows, frames, au) if audio else (rows, frames)
 
@@ -139,10 +129,8 @@ def _analyze(ptr, n_rows, stride, length, window_samples, hop_samples, end_sampl
     else:
         assert out.dtype == np.float64 and out.ndim == 2 and out.shape[0] == n_rows and out.flags.c_contiguous
         whole = False
-    rc = L.ow_centroid_analyze(ptr, int(n_rows), int(stride), int(length), int(window_samples), int(hop_samples), int(end_sample), int(device),
-                               int(is_device), out.ctypes.data_as(C.c_void_p), out.shape[1])
-    if rc < 0:
-        raise OwError(take_error(L))
+    rc = check(L, L.ow_centroid_analyze(ptr, int(n_rows), int(stride), int(length), int(window_samples), int(hop_samples), int(end_sample), int(device),
+                                        int(is_device), out.ctypes.data_as(C.c_void_p), out.shape[1]))
     return out if whole else out[:, :rc]
 
 

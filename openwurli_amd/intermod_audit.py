@@ -11,25 +11,19 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import (INTERMOD_MAX_PROBES, OwError, OwIntermodCfg, OwIntermodReport, OwIntermodRow, OwNoteJob, load_library, take_error)
+from .binding import (INTERMOD_MAX_PROBES, OwError, OwIntermodCfg, OwIntermodDetail, OwIntermodProduct, OwIntermodReport, OwIntermodRow, OwNoteJob, check,
+                      load_library, take_error)  # noqa: F401
 from ._rust_text import _f, midi_note_name, parse_csv_u8, samples  # noqa: F401
 
 MIDI_LO, MIDI_HI = 33, 96                                    # tables.rs:6-7
 VERDICTS = ("DIRTY", "MARGINAL", "OK", "CLEAN")              # ow_intermod_row.verdict
 
 # numpy views of include/openwurli_hip.h ow_note_job / ow_intermod_report / ow_intermod_row
-NOTE_JOB_DTYPE = np.dtype([("note", "u1"), ("velocity", "u1"), ("reserved", "u1", (6,))])
-PRODUCT_DTYPE = np.dtype([("mode", "<u4"), ("nearest_integer", "<u4"), ("mode_ratio", "<f8"), ("fractional_offset", "<f8"), ("beat_hz", "<f8"),
-                          ("effective_amplitude", "<f8"), ("perceptual_weight", "<f8"), ("risk_score", "<f8")])
-REPORT_DTYPE = np.dtype([("midi", "u1"), ("reserved", "u1", (7,)), ("fundamental_hz", "<f8"), ("mu", "<f8"), ("products", PRODUCT_DTYPE, (6,)),
-                         ("max_risk", "<f8"), ("total_risk", "<f8")])
-DETAIL_DTYPE = np.dtype([("mode", "<u4"), ("nearest_integer", "<u4"), ("intermod_freq", "<f8"), ("nearest_freq", "<f8"), ("intermod_mag", "<f8"),
-                         ("nearest_mag", "<f8"), ("ratio_db", "<f8"), ("risk_score", "<f8"), ("listed", "u1"), ("reserved", "u1", (7,))])
-ROW_DTYPE = np.dtype([("midi", "u1"), ("velocity", "u1"), ("too_short", "u1"), ("verdict", "u1"), ("n_harmonics", "<u4"), ("n_midpoints", "<u4"),
-                      ("window_start", "<u4"), ("window_end", "<u4"), ("reserved", "<u4"), ("fundamental_hz", "<f8"), ("harmonic_energy", "<f8"),
-                      ("midpoint_energy", "<f8"), ("h_db", "<f8"), ("m_db", "<f8"), ("ratio_db", "<f8"), ("products", DETAIL_DTYPE, (6,))])
-assert NOTE_JOB_DTYPE.itemsize == C.sizeof(OwNoteJob) and REPORT_DTYPE.itemsize == C.sizeof(OwIntermodReport)
-assert ROW_DTYPE.itemsize == C.sizeof(OwIntermodRow)
+NOTE_JOB_DTYPE = np.dtype(OwNoteJob)
+PRODUCT_DTYPE = np.dtype(OwIntermodProduct)
+REPORT_DTYPE = np.dtype(OwIntermodReport)
+DETAIL_DTYPE = np.dtype(OwIntermodDetail)
+ROW_DTYPE = np.dtype(OwIntermodRow)
 
 
 def note_jobs(notes, velocities=(127,)) -> np.ndarray:
@@ -44,8 +38,7 @@ def risk(midi: int) -> np.void:
     """``ow_intermod_risk`` (host only): the REPORT_DTYPE record of any MIDI byte."""
     L = load_library()
     r = np.zeros(1, dtype=REPORT_DTYPE)
-    if L.ow_intermod_risk(int(midi), C.cast(r.ctypes.data, C.POINTER(OwIntermodReport))) < 0:
-        raise OwError(take_error(L))
+    check(L, L.ow_intermod_risk(int(midi), C.cast(r.ctypes.data, C.POINTER(OwIntermodReport))))
     return r[0]
 
 
@@ -54,9 +47,7 @@ def probes(midi: int):
     L = load_library()
     f = np.zeros(INTERMOD_MAX_PROBES)
     nh, nm = C.c_uint32(0), C.c_uint32(0)
-    c = L.ow_intermod_probes(int(midi), f.ctypes.data_as(C.c_void_p), C.byref(nh), C.byref(nm))
-    if c < 0:
-        raise OwError(take_error(L))
+    c = check(L, L.ow_intermod_probes(int(midi), f.ctypes.data_as(C.c_void_p), C.byref(nh), C.byref(nm)))
     return f[:c].copy(), int(nh.value), int(nm.value)
 
 
@@ -67,9 +58,8 @@ def dft_magnitudes(signals, start, end, freqs, sample_rate=44100.0, device=0) ->
     fr = np.ascontiguousarray(np.atleast_2d(freqs), dtype=np.float64)
     assert fr.shape[0] == sig.shape[0]
     out = np.zeros(fr.shape)
-    if L.ow_dft_magnitudes(sig.ctypes.data_as(C.c_void_p), sig.shape[0], sig.shape[1], int(start), int(end), float(sample_rate),
-                           fr.ctypes.data_as(C.c_void_p), fr.shape[1], int(device), 0, out.ctypes.data_as(C.c_void_p)) < 0:
-        raise OwError(take_error(L))
+    check(L, L.ow_dft_magnitudes(sig.ctypes.data_as(C.c_void_p), sig.shape[0], sig.shape[1], int(start), int(end), float(sample_rate),
+                                 fr.ctypes.data_as(C.c_void_p), fr.shape[1], int(device), 0, out.ctypes.data_as(C.c_void_p)))
     return out
 
 
@@ -81,10 +71,8 @@ def run_jobs(jobs, duration=3.0, device=0, audio=False):
     rows = np.zeros(jb.size, dtype=ROW_DTYPE)
     n = samples(duration)
     au = np.zeros((jb.size, n)) if audio else None
-    rc = L.ow_intermod_audit(jb.ctypes.data_as(C.c_void_p), jb.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
-                             au.ctypes.data_as(C.c_void_p) if audio else None, n)
-    if rc < 0:
-        raise OwError(take_error(L))
+    check(L, L.ow_intermod_audit(jb.ctypes.data_as(C.c_void_p), jb.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
+                                 au.ctypes.data_as(C.c_void_p) if audio else None, n))
     return (rows, au) if audio else rows
 
 

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import OVERSHOOT_ROW_FIELDS, OwError, OwOvershootCfg, OwOvershootRow, load_library, take_error
+from .binding import OVERSHOOT_ROW_FIELDS, OwError, OwOvershootCfg, OwOvershootRow, check, load_library, take_error  # noqa: F401
 from .intermod_audit import NOTE_JOB_DTYPE, note_jobs
 from ._rust_text import _f, midi_note_name, parse_csv_u8, samples  # noqa: F401
 
@@ -18,8 +18,7 @@ DEFAULT_VELOCITIES = (64, 127)                              # main.rs:2149
 DURATION = 2.0                                              # main.rs:2151
 
 # numpy view of include/openwurli_hip.h ow_overshoot_row
-ROW_DTYPE = np.dtype([("note", "u1"), ("velocity", "u1"), ("reserved", "u1", (6,))] + [(f, "<f8") for f in OVERSHOOT_ROW_FIELDS])
-assert ROW_DTYPE.itemsize == C.sizeof(OwOvershootRow)
+ROW_DTYPE = np.dtype(OwOvershootRow)
 
 
 def run_jobs(jobs, duration=DURATION, device=0, audio=False):
@@ -30,10 +29,8 @@ def run_jobs(jobs, duration=DURATION, device=0, audio=False):
     rows = np.zeros(jb.size, dtype=ROW_DTYPE)
     n = samples(duration)
     au = np.zeros((jb.size, n)) if audio else None
-    rc = L.ow_overshoot(jb.ctypes.data_as(C.c_void_p), jb.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
-                        au.ctypes.data_as(C.c_void_p) if audio else None, n)
-    if rc < 0:
-        raise OwError(take_error(L))
+    check(L, L.ow_overshoot(jb.ctypes.data_as(C.c_void_p), jb.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
+                            au.ctypes.data_as(C.c_void_p) if audio else None, n))
     return (rows, au) if audio else rows
 
 

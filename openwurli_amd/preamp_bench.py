@@ -12,17 +12,15 @@ from typing import List, Sequence
 
 import numpy as np
 
-from .binding import PBENCH_SAMPLES, OwError, OwPreampMeasureCfg, OwPreampMeasureRow, OwPreampPoint, load_library, take_error
+from .binding import PBENCH_SAMPLES, OwError, OwPreampMeasureCfg, OwPreampMeasureRow, OwPreampPoint, check, load_library, take_error  # noqa: F401
 
 from ._rust_text import BASE_SR, _f  # noqa: F401
 PREAMP_LEGACY8, PREAMP_MELANGE12 = 0, 1
 R_NEW = 1_000_000.0                                         # the r_ldr DkPreamp::new() solves DC at (dk_preamp_legacy.rs:269-366)
 
 # numpy views of include/openwurli_hip.h ow_preamp_point / ow_preamp_measure_row
-POINT_DTYPE = np.dtype([("freq_hz", "<f8"), ("amplitude", "<f8"), ("r_ldr", "<f8"), ("r_reset", "<f8")])
-ROW_DTYPE = np.dtype([("freq_hz", "<f8"), ("amplitude", "<f8"), ("r_ldr", "<f8"), ("gain", "<f8"), ("gain_db", "<f8"), ("h", "<f8", (5,)),
-                      ("thd_pct", "<f8"), ("h2_h3_db", "<f8")])
-assert POINT_DTYPE.itemsize == C.sizeof(OwPreampPoint) and ROW_DTYPE.itemsize == C.sizeof(OwPreampMeasureRow)
+POINT_DTYPE = np.dtype(OwPreampPoint)
+ROW_DTYPE = np.dtype(OwPreampMeasureRow)
 
 
 def log_spaced(lo: float, hi: float, n: int) -> List[float]:
@@ -93,10 +91,8 @@ def run_points(points: np.ndarray, preamp_kind=PREAMP_LEGACY8, device=0, trace=F
     rows = np.zeros(pts.size, dtype=ROW_DTYPE)
     tr = np.zeros((pts.size, PBENCH_SAMPLES)) if trace else None
     cfg = OwPreampMeasureCfg(int(device), int(preamp_kind))
-    rc = L.ow_preamp_measure(pts.ctypes.data_as(C.c_void_p), pts.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
-                             tr.ctypes.data_as(C.c_void_p) if tr is not None else None, PBENCH_SAMPLES)
-    if rc != 0:
-        raise OwError(take_error(L))
+    check(L, L.ow_preamp_measure(pts.ctypes.data_as(C.c_void_p), pts.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
+                                 tr.ctypes.data_as(C.c_void_p) if tr is not None else None, PBENCH_SAMPLES))
     return (rows, tr) if trace else rows
 
 

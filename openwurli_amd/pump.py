@@ -18,7 +18,7 @@ import time
 
 import numpy as np
 
-from .binding import OwError, OwPumpCfg, OwPumpPoint, OwPumpRow, load_library, take_error
+from .binding import OwError, OwPumpCfg, OwPumpPoint, OwPumpRow, check, load_library, take_error  # noqa: F401
 from .centroid_track import rust_display
 from ._rust_text import _e, _f, as_usize
 
@@ -26,12 +26,10 @@ STATIC, STEP, RAMP, LOGCOS = 0, 1, 2, 3                     # include/openwurli_
 CODEGEN_SR = 48000.0                                        # gen_preamp::SAMPLE_RATE
 
 # numpy views of include/openwurli_hip.h ow_pump_point / ow_pump_row
-POINT_DTYPE = np.dtype([("sample_rate", "<f8"), ("r_settle", "<f8"), ("settle", "<u8"), ("capture", "<u8"), ("in_amp", "<f8"), ("in_freq", "<f8"),
-                        ("extra_sample", "<u4"), ("schedule", "<u4"), ("r_to", "<f8"), ("ln_mid", "<f8"), ("ln_amp", "<f8"), ("sched_freq", "<f8")])
+POINT_DTYPE = np.dtype(OwPumpPoint)
 ROW_FIELDS = ("sum", "sum_sq", "mean", "std", "min", "max", "pair_mean", "pair_std", "raw_std", "extra", "max_step")
 ROW_COUNTERS = ("nr_exhausted", "be_fallbacks", "voltage_damps", "nan_resets")
-ROW_DTYPE = np.dtype([(f, "<f8") for f in ROW_FIELDS] + [(f, "<u8") for f in ROW_COUNTERS])
-assert POINT_DTYPE.itemsize == C.sizeof(OwPumpPoint) and ROW_DTYPE.itemsize == C.sizeof(OwPumpRow)
+ROW_DTYPE = np.dtype(OwPumpRow)
 
 
 def temp_default(filename: str) -> str:
@@ -68,10 +66,8 @@ def run_points(points, device=0, trace=False):
     stride = int(pts["capture"].max()) if pts.size else 0
     tr = np.zeros((pts.size, stride)) if trace else None
     cfg = OwPumpCfg(int(device))
-    rc = L.ow_pump_measure(pts.ctypes.data_as(C.c_void_p), pts.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
-                           tr.ctypes.data_as(C.c_void_p) if trace else None, stride)
-    if rc != 0:
-        raise OwError(take_error(L))
+    check(L, L.ow_pump_measure(pts.ctypes.data_as(C.c_void_p), pts.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p),
+                               tr.ctypes.data_as(C.c_void_p) if trace else None, stride))
     return (rows, tr) if trace else rows
 
 

@@ -14,18 +14,15 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .binding import POLY_MAX_NOTES, WAV_ROUND, OwError, OwPolyCfg, OwPolyChord, OwPolyRow, load_library, take_error
+from .binding import POLY_MAX_NOTES, WAV_ROUND, OwError, OwPolyCfg, OwPolyChord, OwPolyRow, check, load_library, take_error  # noqa: F401
 
 from ._rust_text import BASE_SR, _f, midi_note_name, parse_csv_u8, samples, to_dbfs  # noqa: F401
 WIN_LO, WIN_HI = 8820, 88200                                # (0.2 * BASE_SR) / (2.0 * BASE_SR) as usize, main.rs:1516-1517
 DEFAULT_NOTES, DEFAULT_VELOCITIES = (38, 59, 62, 66), (45, 40, 40, 40)      # main.rs:1398-1399
 
 # numpy views of include/openwurli_hip.h ow_poly_chord / ow_poly_row
-CHORD_DTYPE = np.dtype([("n_notes", "u1"), ("no_poweramp", "u1"), ("reserved", "u1", (6,)), ("notes", "u1", (32,)), ("velocities", "u1", (32,)),
-                        ("volume", "<f8"), ("speaker", "<f8"), ("r_ldr", "<f8")])
-ROW_DTYPE = np.dtype([("peak", "<f8"), ("residual_peak", "<f8"), ("win_peak", "<f8", (3,)), ("win_mean_sq", "<f8", (3,)),
-                      ("peak_db", "<f8", (3,)), ("rms_db", "<f8", (3,)), ("intermod_ratio_db", "<f8")])
-assert CHORD_DTYPE.itemsize == C.sizeof(OwPolyChord) and ROW_DTYPE.itemsize == C.sizeof(OwPolyRow)
+CHORD_DTYPE = np.dtype(OwPolyChord)
+ROW_DTYPE = np.dtype(OwPolyRow)
 
 
 def pad_velocities(notes: Sequence[int], velocities_raw: Sequence[int]) -> list:
@@ -66,10 +63,8 @@ def run_chords(chords, duration=3.0, device=0, final=False, separate_sum=False, 
     audio = {k: np.zeros((ch.size, n)) for k, w in want if w}
     ptr = lambda k: audio[k].ctypes.data_as(C.c_void_p) if k in audio else None
     cfg = OwPolyCfg(float(duration), int(device), int(preamp_kind), int(power_amp_kind))
-    rc = L.ow_render_poly(ch.ctypes.data_as(C.c_void_p), ch.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p), ptr("final"), ptr("separate_sum"),
-                          ptr("residual"), n)
-    if rc < 0:
-        raise OwError(take_error(L))
+    check(L, L.ow_render_poly(ch.ctypes.data_as(C.c_void_p), ch.size, C.byref(cfg), rows.ctypes.data_as(C.c_void_p), ptr("final"), ptr("separate_sum"),
+                              ptr("residual"), n))
     return (rows, audio) if audio else rows
 
 
@@ -137,8 +132,7 @@ def write_wavs(output: str, final, residual, peak: float, residual_peak: float, 
     scale, res_scale = wav_scales(float(peak), float(residual_peak), normalize)
     for path, sig, sc in ((output, final, scale), (residual_path(output), residual, res_scale)):
         sig = np.ascontiguousarray(sig, dtype=np.float64)
-        if L.ow_wav24_write(path.encode(), sig.ctypes.data_as(C.c_void_p), sig.size, int(BASE_SR), float(sc), WAV_ROUND) != 0:
-            raise OwError(take_error(L))
+        check(L, L.ow_wav24_write(path.encode(), sig.ctypes.data_as(C.c_void_p), sig.size, int(BASE_SR), float(sc), WAV_ROUND))
     return scale, res_scale
 
 

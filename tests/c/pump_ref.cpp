@@ -150,26 +150,4 @@ size_t opr_sinusoid_bifurcs(const double* y, size_t samples) {
     return n;
 }
 
-// the header's layouts, for the binding's test: sizes, then offsets of every field in declaration order; returns how many were written
-int opr_layout(int which, size_t* out) {
-    int n = 0;
-#define F(T, f) out[n++] = offsetof(T, f)
-    if (which == 0) {
-        out[n++] = sizeof(ow_pump_point);
-        F(ow_pump_point, sample_rate); F(ow_pump_point, r_settle); F(ow_pump_point, settle); F(ow_pump_point, capture); F(ow_pump_point, in_amp);
-        F(ow_pump_point, in_freq); F(ow_pump_point, extra_sample); F(ow_pump_point, schedule); F(ow_pump_point, r_to); F(ow_pump_point, ln_mid);
-        F(ow_pump_point, ln_amp); F(ow_pump_point, sched_freq);
-    } else if (which == 1) {
-        out[n++] = sizeof(ow_pump_cfg);
-        F(ow_pump_cfg, struct_size); F(ow_pump_cfg, point_size); F(ow_pump_cfg, device); F(ow_pump_cfg, reserved);
-    } else {
-        out[n++] = sizeof(ow_pump_row);
-        F(ow_pump_row, sum); F(ow_pump_row, sum_sq); F(ow_pump_row, mean); F(ow_pump_row, std); F(ow_pump_row, min); F(ow_pump_row, max);
-        F(ow_pump_row, pair_mean); F(ow_pump_row, pair_std); F(ow_pump_row, raw_std); F(ow_pump_row, extra); F(ow_pump_row, max_step);
-        F(ow_pump_row, nr_exhausted); F(ow_pump_row, be_fallbacks); F(ow_pump_row, voltage_damps); F(ow_pump_row, nan_resets);
-    }
-#undef F
-    return n;
-}
-
 }  // extern "C"

@@ -83,7 +83,6 @@ def lib():
             L.opr_trace_stats.restype, L.opr_trace_stats.argtypes = None, [_VP, C.c_size_t, _VP]
             L.opr_step_tail.restype, L.opr_step_tail.argtypes = None, [_VP, C.c_size_t, _VP]
             L.opr_sinusoid_bifurcs.restype, L.opr_sinusoid_bifurcs.argtypes = C.c_size_t, [_VP, C.c_size_t]
-            L.opr_layout.restype, L.opr_layout.argtypes = C.c_int, [C.c_int, _VP]
             _LIB = L
     return _LIB
 
@@ -130,9 +129,3 @@ def sinusoid_bifurcations(buf) -> int:
     b = np.ascontiguousarray(buf, dtype=np.float64)
     return int(lib().opr_sinusoid_bifurcs(b.ctypes.data_as(_VP), b.size))
 
-
-def layout(which):
-    """[sizeof, offsets...] of ow_pump_point (0), ow_pump_cfg (1), ow_pump_row (2) as the C compiler lays the header out."""
-    out = (C.c_size_t * 32)()
-    n = lib().opr_layout(int(which), out)
-    return [int(out[i]) for i in range(n)]

@@ -1,4 +1,4 @@
-"""`preamp-bench bark-audit` without a device: struct layouts against a C compiler, every refusal of ow_bark_audit with its message, the
+"""`preamp-bench bark-audit` without a device: the binding's struct sizes and the restatement's field names, every refusal of ow_bark_audit with its message, the
 returns that need no device, the report's text against a hand-written block, the CSV header, the tool's flags -- and, on the CPU
 restatement (tests/c/bark_audit_ref.cpp), the conditions under which tests/test_gpu_bark_audit.py compares report text exactly.
 """
@@ -17,41 +17,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FN = "ow_bark_audit"
 
 
-# ---- layouts and the ABI ---------------------------------------------------------------------------------------------------------------
-def _c_sizes():
-    """sizeof / offsetof of the new structs as a C compiler sees include/openwurli_hip.h."""
-    import subprocess
-    import tempfile
-    src = r'''#include <stdio.h>
-#include <stddef.h>
-#include "openwurli_hip.h"
-int main(void) {
-    printf("%zu %zu %zu ", sizeof(ow_bark_cfg), sizeof(ow_bark_row), sizeof(ow_note_job));
-    printf("%zu %zu %zu %zu ", offsetof(ow_bark_cfg, duration_s), offsetof(ow_bark_cfg, measure_start_s), offsetof(ow_bark_cfg, device),
-           offsetof(ow_bark_cfg, preamp_kind));
-    printf("%zu %zu %zu %zu %zu %d\n", offsetof(ow_bark_row, window_start), offsetof(ow_bark_row, window_end), offsetof(ow_bark_row, fundamental_hz),
-           offsetof(ow_bark_row, pu_h2_h1), offsetof(ow_bark_row, pre_h2_h1), OW_ABI_VERSION);
-    return 0;
-}'''
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "s.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(d, "s"), os.path.join(d, "s.c")])
-        return [int(x) for x in subprocess.check_output([os.path.join(d, "s")], text=True).split()]
-
-
-def test_struct_layouts_header_binding_numpy(hiplib):
-    from openwurli_amd import binding as b, bark_audit as ba
-    c = _c_sizes()
-    assert c[:3] == [32, 104, 8] == [C.sizeof(b.OwBarkCfg), C.sizeof(b.OwBarkRow), C.sizeof(b.OwNoteJob)]
-    assert ba.ROW_DTYPE.itemsize == 104
-    assert c[3:7] == [b.OwBarkCfg.duration_s.offset, b.OwBarkCfg.measure_start_s.offset, b.OwBarkCfg.device.offset, b.OwBarkCfg.preamp_kind.offset]
-    assert c[7:12] == [b.OwBarkRow.window_start.offset, b.OwBarkRow.window_end.offset, b.OwBarkRow.fundamental_hz.offset, b.OwBarkRow.pu_h2_h1.offset,
-                       b.OwBarkRow.pre_h2_h1.offset]
-    for name, _ in b.OwBarkRow._fields_:
-        assert getattr(b.OwBarkRow, name).offset == ba.ROW_DTYPE.fields[name][1], name
-    assert tuple(ref.FIELDS) == tuple(b.BARK_ROW_FIELDS)
-    assert c[12] == 8 == b.ABI_VERSION == hiplib.ow_abi_version()       # nothing existing changes layout: the version stays
+# ---- the binding's sizes, the restatement's fields, the package's export (against the header: tests/test_abi_layout.py) ------------------------
+def test_struct_layouts_header_binding_numpy():
     import openwurli_amd
+    from openwurli_amd import binding as b, bark_audit as ba
+    assert [32, 104, 8] == [C.sizeof(b.OwBarkCfg), C.sizeof(b.OwBarkRow), C.sizeof(b.OwNoteJob)] and ba.ROW_DTYPE.itemsize == 104
+    assert tuple(ref.FIELDS) == tuple(b.BARK_ROW_FIELDS)
     assert openwurli_amd.bark_audit is ba and "bark_audit" in openwurli_amd.__all__
 
 

@@ -1,18 +1,14 @@
 """Calibration sweep (`preamp-bench calibrate` / `sensitivity`), host side: no GPU needed.
 
-The CPU restatement's table functions against the oracle, the Python configs and CSV writer against the reference's text, the ctypes
-structs against include/openwurli_hip.h, and ow_calibrate's input guards (which refuse before any device work).
+The CPU restatement's table functions against the oracle, the Python configs and CSV writer against the reference's text, and
+ow_calibrate's input guards (which refuse before any device work).  The structs' layouts: tests/test_abi_layout.py.
 """
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import calibrate_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_restated_table_functions_equal_the_oracle_bit_for_bit(oracle):
@@ -94,43 +90,6 @@ def test_write_calibrate_csv_format(tmp_path):
         "33,A1,0,0.5000,0.8800,0.0000,-120.00,-120.00,-120.00,-120.00,-120.00,-120.00,-120.00,-120.00,-120.00,-120.00,-120.00,"
         "-35.00,-1.30,-85.00,0.00\n"
         "96,C7,1,0.8500,0.2412,0.0000,-0.00,-0.00,12.35,0.01,99.99,-0.00,3.00,0.00,1.00,2.00,3.00,-0.00,3.60,0.12,-0.00\n")
-
-
-def _header_struct(name):
-    """(field name, ctypes type, count) of a struct of include/openwurli_hip.h, parsed from the header text."""
-    hdr = open(os.path.join(ROOT, "include", "openwurli_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, flags=re.S).group(1)
-    types = {"uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "double": C.c_double, "int": C.c_int}
-    out = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        t, rest = decl.split(None, 1)
-        for d in rest.split(","):
-            m = re.match(r"\s*(\w+)\s*(?:\[(\d+)\])?\s*$", d)
-            out.append((m.group(1), types[t], int(m.group(2)) if m.group(2) else 0))
-    return out
-
-
-@pytest.mark.parametrize("cname,pyname", [("ow_calib_point", "OwCalibPoint"), ("ow_calibrate_cfg", "OwCalibrateCfg"),
-                                          ("ow_calibrate_row", "OwCalibrateRow")])
-def test_ctypes_structs_match_the_header(cname, pyname):
-    from openwurli_amd import binding, calibrate
-    parsed = _header_struct(cname)
-    Ref = type("Ref", (C.Structure,), {"_fields_": [(n, t * k if k else t) for n, t, k in parsed]})
-    Py = getattr(binding, pyname)
-    assert [f[0] for f in Py._fields_] == [n for n, _, _ in parsed]
-    assert C.sizeof(Py) == C.sizeof(Ref)
-    for n, _, _ in parsed:
-        assert (getattr(Py, n).offset, getattr(Py, n).size) == (getattr(Ref, n).offset, getattr(Ref, n).size), n
-    dt = {"ow_calib_point": calibrate.POINT_DTYPE, "ow_calibrate_row": calibrate.ROW_DTYPE}.get(cname)
-    if dt is not None:
-        assert dt.itemsize == C.sizeof(Ref) and list(dt.names) == [n for n, _, _ in parsed]
-        assert [dt.fields[n][1] for n in dt.names] == [getattr(Ref, n).offset for n, _, _ in parsed]
-    if cname == "ow_calibrate_row":
-        assert list(binding.CALIBRATE_ROW_FIELDS) == [n for n, _, _ in parsed][3:]
 
 
 def _call(lib, points, cfg, taps=None, stride=0):

@@ -1,5 +1,5 @@
 """The recording side's harmonics without a device: the numpy restatement (tests/harmonics_ref.py) against the outputs of the reference's
-own Python (tests/golden/residuals_golden.npz), struct layouts against a C compiler, every refusal of ow_goertzel_harmonics and
+own Python (tests/golden/residuals_golden.npz), the binding's struct sizes, constants and cfg defaults, every refusal of ow_goertzel_harmonics and
 ow_interharmonic_noise with its message, the segment planning of openwurli_amd/harmonics.py against the reference's pattern of skipped
 windows for the seven fixture clips, the WAV reader, and the tools' text from canned results."""
 import ctypes as C
@@ -66,33 +66,14 @@ def test_restatement_noise_and_snr_equal_reference(golden):
     assert ref.snr_window(2205 + 127, 44100.0) is None and ref.snr_window(2205 + 128, 44100.0) == (2205, 2333)
 
 
-# ---- layouts and the ABI ----------------------------------------------------------------------------------------------------------------
-def test_struct_layouts_header_binding(hiplib):
-    import subprocess
-    import tempfile
-    from openwurli_amd import binding as b
-    src = r'''#include <stdio.h>
-#include <stddef.h>
-#include "openwurli_hip.h"
-int main(void) {
-    printf("%zu %zu ", sizeof(ow_harmonics_cfg), sizeof(ow_segment));
-    printf("%zu %zu %zu %zu %zu %zu ", offsetof(ow_harmonics_cfg, segment_size), offsetof(ow_harmonics_cfg, sample_rate), offsetof(ow_harmonics_cfg, search_pct),
-           offsetof(ow_harmonics_cfg, wav24_mode), offsetof(ow_harmonics_cfg, device), offsetof(ow_harmonics_cfg, audio_is_device));
-    printf("%d %d %d %d\n", OW_GOERTZEL_OFFSETS, OW_NOISE_MAX_BAND_BINS, OW_MAX_HARMONICS, OW_ABI_VERSION);
-    return 0;
-}'''
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "s.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(d, "s"), os.path.join(d, "s.c")])
-        c = [int(x) for x in subprocess.check_output([os.path.join(d, "s")], text=True).split()]
-    Cfg = b.OwHarmonicsCfg
-    assert c[:2] == [40, 24] == [C.sizeof(Cfg), np.dtype(b.SEGMENT_DTYPE).itemsize]
-    assert c[2:8] == [Cfg.segment_size.offset, Cfg.sample_rate.offset, Cfg.search_pct.offset, Cfg.wav24_mode.offset, Cfg.device.offset, Cfg.audio_is_device.offset]
-    assert c[8:11] == [b.GOERTZEL_OFFSETS, b.NOISE_MAX_BAND_BINS, b.MAX_HARMONICS] == [ref.N_OFFSETS, 4096, 8]
-    assert c[11] == 8 == b.ABI_VERSION == hiplib.ow_abi_version()       # nothing existing changes layout: the version stays
-    cfg = Cfg()
-    assert (cfg.struct_size, cfg.segment_size, cfg.sample_rate, cfg.search_pct, cfg.wav24_mode, cfg.audio_is_device) == (40, 24, 44100.0, 0.01, b.WAV_NONE, 0)
+# ---- the binding's sizes, constants, defaults and exports (against the header: tests/test_abi_layout.py) -------------------------------------
+def test_struct_layouts_header_binding():
     import openwurli_amd
+    from openwurli_amd import binding as b
+    assert [40, 24] == [C.sizeof(b.OwHarmonicsCfg), b.SEGMENT_DTYPE.itemsize]
+    assert [b.GOERTZEL_OFFSETS, b.NOISE_MAX_BAND_BINS, b.MAX_HARMONICS] == [ref.N_OFFSETS, 4096, 8]
+    cfg = b.OwHarmonicsCfg()
+    assert (cfg.struct_size, cfg.segment_size, cfg.sample_rate, cfg.search_pct, cfg.wav24_mode, cfg.audio_is_device) == (40, 24, 44100.0, 0.01, b.WAV_NONE, 0)
     assert {"harmonics", "residuals"} <= set(openwurli_amd.__all__) and {"ow_goertzel_harmonics", "ow_interharmonic_noise"} <= set(b.SYMBOLS)
 
 

@@ -1,5 +1,5 @@
 """Recorded-note intake without a device: the Python restatement (tests/isolation_ref.py) against the outputs of the reference's own
-Python (tests/golden/isolation_golden.json, tests/golden/intake_golden.npz) bit for bit, struct layouts against a C compiler, window
+Python (tests/golden/isolation_golden.json, tests/golden/intake_golden.npz) bit for bit, the binding's struct sizes, window
 planning, id keys and file grouping of openwurli_amd/isolation.py, the decay and collision tables against the restatement, the report
 text, the tools' argument surface, and every refusal of ow_isolation_score / ow_clip_bounds that is decided before the device is touched."""
 import ctypes as C
@@ -80,33 +80,11 @@ def test_restatement_intake_equals_the_reference(intake):
             assert [first, last] == list(intake[f"clip_idx{i}"]), i
 
 
-# ---- layouts ----------------------------------------------------------------------------------------------------------------------------------
-def test_struct_layouts_header_binding(hiplib):
-    import subprocess
-    import tempfile
-    from openwurli_amd import binding as b
-    src = r'''#include <stdio.h>
-#include <stddef.h>
-#include "openwurli_hip.h"
-int main(void) {
-    printf("%zu %zu ", sizeof(ow_iso_note), sizeof(ow_iso_cfg));
-    printf("%zu %zu %zu %zu %zu ", offsetof(ow_iso_note, window_start), offsetof(ow_iso_note, window_end), offsetof(ow_iso_note, id_key),
-           offsetof(ow_iso_note, midi_note), offsetof(ow_iso_note, score));
-    printf("%zu %zu %zu %zu %zu %zu %d\n", offsetof(ow_iso_cfg, note_size), offsetof(ow_iso_cfg, device), offsetof(ow_iso_cfg, collision_ratio),
-           offsetof(ow_iso_cfg, decay_rate), offsetof(ow_iso_cfg, midi_freq), offsetof(ow_iso_cfg, kernel_ms_out), OW_ABI_VERSION);
-    return 0;
-}'''
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "s.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(d, "s"), os.path.join(d, "s.c")])
-        c = [int(x) for x in subprocess.check_output([os.path.join(d, "s")], text=True).split()]
-    N, Cfg = b.OwIsoNote, b.OwIsoCfg
-    assert c[:2] == [56, 48] == [C.sizeof(N), C.sizeof(Cfg)] and np.dtype(b.ISO_NOTE_DTYPE).itemsize == 56
-    assert c[2:7] == [N.window_start.offset, N.window_end.offset, N.id_key.offset, N.midi_note.offset, N.score.offset]
-    assert c[2:7] == [np.dtype(b.ISO_NOTE_DTYPE).fields[k][1] for k in ("window_start", "window_end", "id_key", "midi_note", "score")]
-    assert c[7:13] == [Cfg.note_size.offset, Cfg.device.offset, Cfg.collision_ratio.offset, Cfg.decay_rate.offset, Cfg.midi_freq.offset, Cfg.kernel_ms_out.offset]
-    assert c[13] == b.ABI_VERSION == 8                    # entry points only: the version stays
+# ---- the binding's sizes and the exports (against the header: tests/test_abi_layout.py) ---------------------------------------------------------
+def test_struct_layouts_header_binding():
     import openwurli_amd
+    from openwurli_amd import binding as b
+    assert [56, 48] == [C.sizeof(b.OwIsoNote), C.sizeof(b.OwIsoCfg)] and b.ISO_NOTE_DTYPE.itemsize == 56
     assert {"isolation", "note_intake"} <= set(openwurli_amd.__all__)
     assert {"ow_isolation_score", "ow_isolation_collision_table", "ow_clip_bounds"} <= set(b.SYMBOLS)
 

@@ -1,4 +1,4 @@
-"""MLP training without a device: struct layouts against a C compiler, every refusal of ow_mlp_train with its message, load_data and
+"""MLP training without a device: the binding's struct sizes and cfg defaults, every refusal of ow_mlp_train with its message, load_data and
 init_like_reference against direct restatements, the precondition of the GPU tests' whole runs (torch's own result does not move with the
 order of the rows), and the tool's text from canned results.
 
@@ -8,9 +8,7 @@ import ctypes as C
 import io
 import json
 import os
-import subprocess
 import sys
-import tempfile
 from contextlib import redirect_stdout
 
 import numpy as np
@@ -22,50 +20,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FN = "ow_mlp_train"
 
 
-# ---- layouts and the ABI ---------------------------------------------------------------------------------------------------------------
-def _c_sizes():
-    src = r'''#include <stdio.h>
-#include <stddef.h>
-#include "openwurli_hip.h"
-int main(void) {
-    printf("%zu %zu %zu ", sizeof(ow_mlp_train_model), sizeof(ow_mlp_train_cfg), sizeof(ow_mlp_train_result));
-    printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu ", offsetof(ow_mlp_train_model, lr), offsetof(ow_mlp_train_model, min_lr), offsetof(ow_mlp_train_model, weight_decay),
-           offsetof(ow_mlp_train_model, huber_delta), offsetof(ow_mlp_train_model, sched_factor), offsetof(ow_mlp_train_model, epochs),
-           offsetof(ow_mlp_train_model, patience), offsetof(ow_mlp_train_model, sched_patience), offsetof(ow_mlp_train_model, target_mask));
-    printf("%zu %zu %zu %zu %zu %zu ", offsetof(ow_mlp_train_cfg, struct_size), offsetof(ow_mlp_train_cfg, model_size), offsetof(ow_mlp_train_cfg, device),
-           offsetof(ow_mlp_train_cfg, n_rows), offsetof(ow_mlp_train_cfg, history_epochs), offsetof(ow_mlp_train_cfg, kernel_ms_out));
-    printf("%zu %zu %zu %zu %zu %zu %zu %zu ", offsetof(ow_mlp_train_result, best_val_loss), offsetof(ow_mlp_train_result, last_train_loss),
-           offsetof(ow_mlp_train_result, last_val_loss), offsetof(ow_mlp_train_result, last_lr), offsetof(ow_mlp_train_result, best_epoch),
-           offsetof(ow_mlp_train_result, epochs_run), offsetof(ow_mlp_train_result, lr_reductions), offsetof(ow_mlp_train_result, status));
-    printf("%d %u\n", OW_ABI_VERSION, OW_MLP_TRAIN_MAX_ROW_EPOCHS);
-    return 0;
-}'''
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "s.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(d, "s"), os.path.join(d, "s.c")])
-        return [int(x) for x in subprocess.check_output([os.path.join(d, "s")], text=True).split()]
-
-
-def test_struct_layouts_header_binding_numpy(hiplib):
-    from openwurli_amd import binding as b
-    c = _c_sizes()
-    M, Cf, R = b.OwMlpTrainModel, b.OwMlpTrainCfg, b.OwMlpTrainResult
-    assert c[:3] == [56, 32, 48] == [C.sizeof(M), C.sizeof(Cf), C.sizeof(R)]
-    assert c[3:12] == [getattr(M, n).offset for n, _ in M._fields_]
-    assert c[12:18] == [Cf.struct_size.offset, Cf.model_size.offset, Cf.device.offset, Cf.n_rows.offset, Cf.history_epochs.offset, Cf.kernel_ms_out.offset]
-    assert c[18:26] == [getattr(R, n).offset for n, _ in R._fields_]
-    md, rd = np.dtype(b.MLP_TRAIN_MODEL_DTYPE), np.dtype(b.MLP_TRAIN_RESULT_DTYPE)
-    assert md.itemsize == 56 and rd.itemsize == 48
-    for n, _ in M._fields_:
-        assert md.fields[n][1] == getattr(M, n).offset, n
-    for n, _ in R._fields_:
-        assert rd.fields[n][1] == getattr(R, n).offset, n
-    assert c[26] == 8 == b.ABI_VERSION == hiplib.ow_abi_version()       # nothing existing changes layout: the version stays
-    assert c[27] == 1 << 26 == b.MLP_TRAIN_MAX_ROW_EPOCHS
-    cfg = Cf(70, 12, 1)
-    assert (cfg.struct_size, cfg.model_size, cfg.n_rows, cfg.history_epochs, cfg.device) == (32, 56, 70, 12, 1) and not cfg.kernel_ms_out
+# ---- the binding's sizes, cfg defaults and exports (against the header: tests/test_abi_layout.py) ----------------------------------------------
+def test_struct_layouts_header_binding_numpy():
     import openwurli_amd
-    from openwurli_amd import mlp_train
+    from openwurli_amd import binding as b, mlp_train
+    assert [56, 32, 48] == [C.sizeof(b.OwMlpTrainModel), C.sizeof(b.OwMlpTrainCfg), C.sizeof(b.OwMlpTrainResult)]
+    assert b.MLP_TRAIN_MODEL_DTYPE.itemsize == 56 and b.MLP_TRAIN_RESULT_DTYPE.itemsize == 48 and b.MLP_TRAIN_MAX_ROW_EPOCHS == 1 << 26
+    cfg = b.OwMlpTrainCfg(70, 12, 1)
+    assert (cfg.struct_size, cfg.model_size, cfg.n_rows, cfg.history_epochs, cfg.device) == (32, 56, 70, 12, 1) and not cfg.kernel_ms_out
     assert openwurli_amd.mlp_train is mlp_train and "mlp_train" in openwurli_amd.__all__ and "ow_mlp_train" in b.SYMBOLS
 
 

@@ -1,8 +1,8 @@
 """Preamp measurements (`preamp-bench gain` / `sweep` / `harmonics` / `tremolo-sweep`), host side: no GPU needed.
 
 The CPU restatement (tests/c/preamp_bench_ref.cpp) against the per-point model the device runs (r_reset), the reference's own gain
-assertions and published figures on the restatement, the Python point builders and text formats against main.rs, the ctypes structs
-against include/openwurli_hip.h, and ow_preamp_measure's input guards (which refuse before any device work).
+assertions and published figures on the restatement, the Python point builders and text formats against main.rs, and
+ow_preamp_measure's input guards (which refuse before any device work).  The structs' layouts: tests/test_abi_layout.py.
 """
 import ctypes as C
 import math
@@ -135,40 +135,6 @@ def test_text_formats():
     assert hl[-1] == "  H2/H3:       inf dB  (target: H2 > H3, i.e. > 0 dB)"
     assert pb.format_surface_csv([20.0], [19_000.0], np.array([[6.0]])) == "ldr_ohm,freq_hz,gain_db\n19000,20.0,6.00\n"
     assert pb.target_db(500_000.0) == 12.1 and pb.target_db(500_000.5) == 6.0
-
-
-def _header_struct(name):
-    hdr = open(os.path.join(ROOT, "include", "openwurli_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, flags=re.S).group(1)
-    types = {"uint32_t": C.c_uint32, "double": C.c_double, "int": C.c_int}
-    out = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        t, rest = decl.split(None, 1)
-        for d in rest.split(","):
-            m = re.match(r"\s*(\w+)\s*(?:\[(\d+)\])?\s*$", d)
-            out.append((m.group(1), types[t], int(m.group(2)) if m.group(2) else 0))
-    return out
-
-
-@pytest.mark.parametrize("cname,pyname", [("ow_preamp_point", "OwPreampPoint"), ("ow_preamp_measure_cfg", "OwPreampMeasureCfg"),
-                                          ("ow_preamp_measure_row", "OwPreampMeasureRow")])
-def test_ctypes_structs_match_the_header(cname, pyname):
-    from openwurli_amd import binding, preamp_bench
-    parsed = _header_struct(cname)
-    Ref = type("Ref", (C.Structure,), {"_fields_": [(n, t * k if k else t) for n, t, k in parsed]})
-    Py = getattr(binding, pyname)
-    assert [f[0] for f in Py._fields_] == [n for n, _, _ in parsed]
-    assert C.sizeof(Py) == C.sizeof(Ref)
-    for n, _, _ in parsed:
-        assert (getattr(Py, n).offset, getattr(Py, n).size) == (getattr(Ref, n).offset, getattr(Ref, n).size), n
-    dt = {"ow_preamp_point": preamp_bench.POINT_DTYPE, "ow_preamp_measure_row": preamp_bench.ROW_DTYPE}.get(cname)
-    if dt is not None:
-        assert dt.itemsize == C.sizeof(Ref) and list(dt.names) == [n for n, _, _ in parsed]
-        assert [dt.fields[n][1] for n in dt.names] == [getattr(Ref, n).offset for n, _, _ in parsed]
 
 
 def test_window_constants_match_the_header():

@@ -1,5 +1,5 @@
 """The pump measurements without a device: the CPU restatement (tests/pump_ref.py) against what the reference's pump commands are known to
-show, its own one-ulp sensitivity at every shape the GPU tests use, the binding's struct layouts, every refusal of ow_pump_measure, the
+show, its own one-ulp sensitivity at every shape the GPU tests use, the row's field tuples, every refusal of ow_pump_measure, the
 commands' text from fixed numbers, and the points each command builds."""
 import ctypes as C
 import math
@@ -59,15 +59,10 @@ def test_restatement_row_is_the_reduction_of_its_trace():
     assert row["mean"] == row["sum"] / 33
 
 
-# ---- layouts ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("which, ctype, dtype", [(0, binding.OwPumpPoint, pump.POINT_DTYPE), (1, binding.OwPumpCfg, None), (2, binding.OwPumpRow, pump.ROW_DTYPE)])
-def test_struct_layouts_match_the_header(which, ctype, dtype):
-    lay = ref.layout(which)
-    assert lay[0] == C.sizeof(ctype)
-    assert lay[1:] == [getattr(ctype, f).offset for f, *_ in ctype._fields_]
-    if dtype is not None:
-        assert dtype.itemsize == lay[0] and [dtype.fields[f][1] for f in dtype.names] == lay[1:]
-        assert list(dtype.names) == [f for f, *_ in ctype._fields_]
+# ---- the row's field tuples (the structs' layouts: tests/test_abi_layout.py) -------------------------------------------------------------------
+def test_row_field_tuples_are_the_rows_fields():
+    assert pump.ROW_FIELDS + pump.ROW_COUNTERS == pump.ROW_DTYPE.names == tuple(f for f, _ in binding.OwPumpRow._fields_)
+    assert all(pump.ROW_DTYPE[f] == np.float64 for f in pump.ROW_FIELDS) and all(pump.ROW_DTYPE[f] == np.uint64 for f in pump.ROW_COUNTERS)
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------------------------

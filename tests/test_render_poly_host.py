@@ -2,20 +2,16 @@
 
 The CPU restatement (tests/c/render_poly_ref.cpp) against the existing oracle's batch job where the two commands coincide, and where they
 must not (the reset order); the sample floor of the GPU test under the project's floor rule, measured here; the condition that keeps the
-GPU test's intermod_ratio_db assertion honest; the Python report, padding, verdict and WAV logic against main.rs; the ctypes structs
-against include/openwurli_hip.h; and ow_render_poly's refusals, which come before any device work.
+GPU test's intermod_ratio_db assertion honest; the Python report, padding, verdict and WAV logic against main.rs; the restatement's row
+against the binding's (the structs' layouts: tests/test_abi_layout.py); and ow_render_poly's refusals, which come before any device work.
 """
 import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
 import render_poly_ref as ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -194,40 +190,9 @@ def test_wav_scales_and_files(hiplib_host, tmp_path):
 
 
 # ---- the C-ABI --------------------------------------------------------------------------------------------------------------------
-def _header_struct(name):
-    hdr = open(os.path.join(ROOT, "include", "openwurli_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, flags=re.S).group(1)
-    types = {"uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "double": C.c_double, "int": C.c_int}
-    out = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        t, rest = decl.split(None, 1)
-        for d in rest.split(","):
-            m = re.match(r"\s*(\w+)\s*(?:\[(\d+)\])?\s*$", d)
-            out.append((m.group(1), types[t], int(m.group(2)) if m.group(2) else 0))
-    return out
-
-
-@pytest.mark.parametrize("cname,pyname", [("ow_poly_chord", "OwPolyChord"), ("ow_poly_cfg", "OwPolyCfg"), ("ow_poly_row", "OwPolyRow")])
-def test_ctypes_structs_match_the_header(cname, pyname):
-    from openwurli_amd import binding, render_poly
-    parsed = _header_struct(cname)
-    Ref = type("Ref", (C.Structure,), {"_fields_": [(n, t * k if k else t) for n, t, k in parsed]})
-    Py = getattr(binding, pyname)
-    assert [f[0] for f in Py._fields_] == [n for n, _, _ in parsed]
-    assert C.sizeof(Py) == C.sizeof(Ref)
-    for n, _, _ in parsed:
-        assert (getattr(Py, n).offset, getattr(Py, n).size) == (getattr(Ref, n).offset, getattr(Ref, n).size), n
-    dt = {"ow_poly_chord": render_poly.CHORD_DTYPE, "ow_poly_row": render_poly.ROW_DTYPE}.get(cname)
-    if dt is not None:
-        assert dt.itemsize == C.sizeof(Ref) and list(dt.names) == [n for n, _, _ in parsed]
-        assert [dt.fields[n][1] for n in dt.names] == [getattr(Ref, n).offset for n, _, _ in parsed]
-    hdr = open(os.path.join(ROOT, "include", "openwurli_hip.h")).read()
-    assert int(re.search(r"#define OW_POLY_MAX_NOTES (\d+)", hdr).group(1)) == binding.POLY_MAX_NOTES == 31
-    assert list(ref.ROW) == [n for n, _, _ in _header_struct("ow_poly_row")]
+def test_restatement_row_is_the_bindings_row():
+    from openwurli_amd import binding
+    assert list(ref.ROW) == [f[0] for f in binding.OwPolyRow._fields_]      # which tests/test_abi_layout.py holds to the header's declarators
 
 
 def _call(lib, chords, cfg, final=None, stride=0):
