@@ -1,6 +1,6 @@
-"""ctypes loader of the CPU restatement of `preamp-bench bark-audit` (tests/c/bark_audit_ref.cpp, over the oracle's headers).  It is
-compiled on first use with the oracle Makefile's flags into a temporary directory; nothing of it is kept in the tree.  A second build with
--DOW_ORACLE_VOICE_PERTURB (the voice's library calls off by one ulp, oracle/ow_voice.hpp) is the sensitivity variant.
+"""ctypes loader of the CPU restatement of `preamp-bench bark-audit` (tests/c/bark_audit_ref.cpp, over the oracle's headers).
+tests/native.py has oracle/Makefile build it into oracle/_build when it is out of date, and declares its functions from that source.  A
+second build with -DOW_ORACLE_VOICE_PERTURB (the voice's library calls off by one ulp, oracle/ow_voice.hpp) is the sensitivity variant.
 
 Also here, because the host and the GPU tests share them: the jobs the GPU tests run, the bars, and the report's text built from the
 restatement's numbers.
@@ -14,27 +14,21 @@ a-priori bound of an n-term sum: a magnitude's bar is B + B_a, a ratio's gains r
 """
 import ctypes as C
 import math
-import os
-import subprocess
-import tempfile
 import threading
 from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+import native
 from note_audit_ref import analysis_cap, clear_of_rounding  # noqa: F401  (one definition of each for the audits)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]      # oracle/Makefile
 BASE_SR = 44100.0
 SECOND_ORDER = 1.5
 PARITY_REL, PARITY_FLOOR_FRAC = 1e-5, 1e-3      # oracle_binding.parity_report's defaults
-_LIBS = {}
 _LOCK = threading.Lock()
 _WARM = set()
-_VP, _D, _Z, _I = C.c_void_p, C.c_double, C.c_size_t, C.c_int
+_VP = C.c_void_p
 
 FIELDS = ("fundamental_hz", "displacement_scale", "reed_peak", "y_peak", "pu_peak", "pu_h1", "pu_h2", "pu_h2_h1", "pre_h1", "pre_h2", "pre_h2_h1")
 Row = namedtuple("Row", FIELDS)
@@ -56,17 +50,7 @@ TEXT_JOBS = {DEFAULT_SIZE: ((33, 127), (48, 100), (60, 40), (72, 127), (84, 80),
 
 
 def lib(perturbed=False):
-    with _LOCK:
-        if perturbed not in _LIBS:
-            out = os.path.join(tempfile.mkdtemp(prefix="barkref_"), "libbark_audit_ref%s.so" % ("_perturbed" if perturbed else ""))
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + (["-DOW_ORACLE_VOICE_PERTURB"] if perturbed else []) +
-                                  ["-shared", "-I", os.path.join(ROOT, "oracle"), "-o", out, os.path.join(HERE, "c", "bark_audit_ref.cpp"), "-lm"])
-            L = C.CDLL(out)
-            L.obr_samples.restype, L.obr_samples.argtypes = _Z, [_D]
-            L.obr_dft_magnitude.restype, L.obr_dft_magnitude.argtypes = _D, [_VP, _Z, _D, _D]
-            L.obr_run.restype, L.obr_run.argtypes = _Z, [_I, _I, _D, _D, _I, _VP, _VP]
-            _LIBS[perturbed] = L
-    return _LIBS[perturbed]
+    return native.load("bark_audit_ref", "voice_perturbed" if perturbed else "")
 
 
 def samples(seconds):

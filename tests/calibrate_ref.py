@@ -1,41 +1,20 @@
 """ctypes loader of the CPU restatement of `preamp-bench calibrate` (tests/c/calibrate_ref.cpp, over the oracle's headers).
 
-It is compiled on first use with the oracle Makefile's flags into a temporary directory; nothing of it is kept in the tree.
+tests/native.py has oracle/Makefile build it into oracle/_build when it is out of date, and declares its functions from that source.
 """
 import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]      # oracle/Makefile
+import native
+
 N_SAMPLES = 22050
-_LIB = None
-_LOCK = threading.Lock()
 _WARM = set()
 
 
 def lib():
-    global _LIB
-    with _LOCK:
-        if _LIB is None:
-            out = os.path.join(tempfile.mkdtemp(prefix="calref_"), "libcalibrate_ref.so")
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + ["-shared", "-I", os.path.join(ROOT, "oracle"), "-o", out,
-                                                                          os.path.join(HERE, "c", "calibrate_ref.cpp"), "-lm"])
-            L = C.CDLL(out)
-            L.ocal_pickup_displacement_scale.restype = C.c_double
-            L.ocal_pickup_displacement_scale.argtypes = [C.c_int, C.c_void_p, C.c_int]
-            L.ocal_output_scale.restype = C.c_double
-            L.ocal_output_scale.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_int]
-            L.ocal_run_point.restype = None
-            L.ocal_run_point.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-            _LIB = L
-    return _LIB
+    return native.load("calibrate_ref")
 
 
 def cfg6(cfg):

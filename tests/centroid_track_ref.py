@@ -1,7 +1,7 @@
 """ctypes loader of the CPU restatement of `preamp-bench centroid-track` (tests/c/centroid_track_ref.cpp, over the oracle's headers).
 
-It is compiled on first use with the oracle Makefile's flags into a temporary directory; nothing of it is kept in the tree.  A second build
-with -DOW_ORACLE_EXP_PERTURB (the BJT exp() off by one ulp, oracle/ow_chain.hpp) is the sensitivity variant.
+tests/native.py has oracle/Makefile build it into oracle/_build when it is out of date, and declares its functions from that source.  A
+second build with -DOW_ORACLE_EXP_PERTURB (the BJT exp() off by one ulp, oracle/ow_chain.hpp) is the sensitivity variant.
 
 Also here, because both the host and the GPU tests use them: the jobs the GPU parity test runs (JOBS), and the bars.
 
@@ -15,22 +15,15 @@ with b_i the batch path's sample bars (oracle.parity_report's, ABS_FLOOR_BATCH).
 factor covers the second-order terms) plus the analysis bar ANALYSIS_REL x c, which covers the device's sin / cos against the host's.
 """
 import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
 from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]      # oracle/Makefile
+import native
+
 BASE_SR = 44100.0
-_LIBS = {}
-_LOCK = threading.Lock()
-_VP, _D, _Z = C.c_void_p, C.c_double, C.c_size_t
+_VP, _Z = C.c_void_p, C.c_size_t
 
 Job = namedtuple("Job", "note velocity volume speaker ldr no_preamp no_poweramp displacement_scale")
 Job.__new__.__defaults__ = (0.60, 1.0, 1e6, False, False, None)
@@ -59,24 +52,7 @@ ONE_HZ_SHARE = 0.90          # the condition: at least this share of a job's fra
 
 
 def lib(perturbed=False):
-    with _LOCK:
-        if perturbed not in _LIBS:
-            out = os.path.join(tempfile.mkdtemp(prefix="ctref_"), "libcentroid_track_ref%s.so" % ("_perturbed" if perturbed else ""))
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + (["-DOW_ORACLE_EXP_PERTURB"] if perturbed else []) +
-                                  ["-shared", "-I", os.path.join(ROOT, "oracle"), "-o", out, os.path.join(HERE, "c", "centroid_track_ref.cpp"), "-lm"])
-            L = C.CDLL(out)
-            L.oct_samples.restype = _Z
-            L.oct_samples.argtypes = [_D]
-            L.oct_ms_to_samples.restype = _Z
-            L.oct_ms_to_samples.argtypes = [_D]
-            L.oct_bins.restype = C.c_longlong
-            L.oct_bins.argtypes = [_Z, C.POINTER(_Z), C.POINTER(_Z)]
-            L.oct_render.restype = _Z
-            L.oct_render.argtypes = [C.c_int, C.c_int, _D, _D, _D, _D, C.c_int, C.c_int, C.c_int, _D, _VP, _Z]
-            L.oct_analyze.restype = _Z
-            L.oct_analyze.argtypes = [_VP, _Z, _Z, _Z, _Z, _VP, _VP, _Z]
-            _LIBS[perturbed] = L
-    return _LIBS[perturbed]
+    return native.load("centroid_track_ref", "perturbed" if perturbed else "")
 
 
 def samples(duration):

@@ -1,45 +1,30 @@
 """ctypes loader of the CPU restatement of a render with run-time MLP corrections (tests/c/mlp_eval_ref.cpp, over the oracle's headers).
-It is compiled on first use with the oracle Makefile's flags into a temporary directory; nothing of it is kept in the tree.
+tests/native.py has oracle/Makefile build it into oracle/_build when it is out of date, and declares its functions from that source.
 
 Also here, because the host and the GPU tests share them: the weight sets, the points and the jobs the tests use, and the restatement's
 renders, computed once per process and never modified.
 """
 import ctypes as C
-import os
-import subprocess
-import tempfile
 import threading
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]      # oracle/Makefile
+import native
+
 SR = 44100.0
 N_WEIGHTS = 529
 IDENTITY = np.array([0.0] * 5 + [1.0] * 5 + [1.0])
 CLAMP_LO = np.array([-100.0] * 5 + [0.3] * 5 + [0.7])        # mlp_correction.rs:118-132
 CLAMP_HI = np.array([100.0] * 5 + [3.0] * 5 + [1.2])
-_LIB = None
 _LOCK = threading.Lock()
-_VP, _D, _Z, _I = C.c_void_p, C.c_double, C.c_size_t, C.c_int
+_VP = C.c_void_p
 
 
 def lib():
-    global _LIB
-    with _LOCK:
-        if _LIB is None:
-            out = os.path.join(tempfile.mkdtemp(prefix="mlpref_"), "libmlp_eval_ref.so")
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS +
-                                  ["-shared", "-I", os.path.join(ROOT, "oracle"), "-o", out, os.path.join(HERE, "c", "mlp_eval_ref.cpp"), "-lm"])
-            L = C.CDLL(out)
-            L.omr_infer.restype, L.omr_infer.argtypes = None, [_VP, _I, _D, _VP, _VP]
-            L.omr_weights_doubles.restype, L.omr_weights_doubles.argtypes = _Z, []
-            L.omr_render.restype, L.omr_render.argtypes = _Z, [_I, _I, _D, _D, _VP, C.c_uint, _I, _I, _VP, _VP, _Z]
-            assert L.omr_weights_doubles() == N_WEIGHTS
-            _LIB = L
-    return _LIB
+    L = native.load("mlp_eval_ref")
+    assert L.omr_weights_doubles() == N_WEIGHTS
+    return L
 
 
 def fade(note):

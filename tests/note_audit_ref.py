@@ -1,7 +1,7 @@
 """ctypes loader of the CPU restatement of `preamp-bench intermod-audit` and `overshoot` (tests/c/note_audit_ref.cpp, over the oracle's
-headers).  It is compiled on first use with the oracle Makefile's flags into a temporary directory; nothing of it is kept in the tree.  A
-second build with -DOW_ORACLE_VOICE_PERTURB (the voice's library calls off by one ulp, oracle/ow_voice.hpp) is the sensitivity variant of
-the voice row.
+headers).  tests/native.py has oracle/Makefile build it into oracle/_build when it is out of date, and declares its functions from that
+source.  A second build with -DOW_ORACLE_VOICE_PERTURB (the voice's library calls off by one ulp, oracle/ow_voice.hpp) is the sensitivity
+variant of the voice row.
 
 Also here, because the host and the GPU tests share them: the jobs the GPU tests run, the bars, and the reports' text built from the
 restatement's numbers.
@@ -14,23 +14,18 @@ sin / cos against the serial host loop), which enters the same way with B_a = AN
 """
 import ctypes as C
 import math
-import os
-import subprocess
-import tempfile
 import threading
 from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]      # oracle/Makefile
+import native
+
 BASE_SR = 44100.0
 MAX_PROBES = 75
-_LIBS = {}
 _LOCK = threading.Lock()
-_VP, _D, _Z, _I = C.c_void_p, C.c_double, C.c_size_t, C.c_int
+_VP = C.c_void_p
 
 VOICE_REL = 1e-10            # tests/test_gpu_parity.py test_render_note: |gpu - cpu| <= 1e-10 x peak|cpu| on every sample
 SECOND_ORDER = 1.5
@@ -67,22 +62,7 @@ OVERSHOOT_JOBS = ((36, 64), (36, 127), (84, 64), (84, 127))
 
 
 def lib(perturbed=False):
-    with _LOCK:
-        if perturbed not in _LIBS:
-            out = os.path.join(tempfile.mkdtemp(prefix="naref_"), "libnote_audit_ref%s.so" % ("_perturbed" if perturbed else ""))
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + (["-DOW_ORACLE_VOICE_PERTURB"] if perturbed else []) +
-                                  ["-shared", "-I", os.path.join(ROOT, "oracle"), "-o", out, os.path.join(HERE, "c", "note_audit_ref.cpp"), "-lm"])
-            L = C.CDLL(out)
-            L.onr_samples.restype, L.onr_samples.argtypes = _Z, [_D]
-            L.onr_intermod_risk.restype, L.onr_intermod_risk.argtypes = None, [_I, _VP]
-            L.onr_perceptual_beat_weight.restype, L.onr_perceptual_beat_weight.argtypes = _D, [_D]
-            L.onr_dft_magnitude.restype, L.onr_dft_magnitude.argtypes = _D, [_VP, _Z, _D, _D]
-            L.onr_render.restype, L.onr_render.argtypes = _Z, [_I, _I, _D, _VP, _Z]
-            L.onr_probes.restype, L.onr_probes.argtypes = _I, [_I, _VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-            L.onr_intermod_audit.restype, L.onr_intermod_audit.argtypes = _I, [_VP, _Z, _I, _VP, _VP]
-            L.onr_overshoot.restype, L.onr_overshoot.argtypes = None, [_VP, _Z, _VP, _VP]
-            _LIBS[perturbed] = L
-    return _LIBS[perturbed]
+    return native.load("note_audit_ref", "voice_perturbed" if perturbed else "")
 
 
 def samples(duration):

@@ -4,74 +4,30 @@ Test infrastructure only: imported by tests/, __graft_entry__.smoke() and bench.
 cpu_baseline leg -- never by the product package.
 """
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_PATH = os.path.join(_ROOT, "oracle", "_build", "libow_oracle.so")
-_PATH_PERTURBED = os.path.join(_ROOT, "oracle", "_build", "libow_oracle_perturbed.so")
-_LIB = None
-_LIB_P = None
+import native
 
 
 def build():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(_ROOT, "oracle")])
-
-
-def _configure(L):
-    if True:
-        L.owo_engine_new.restype = C.c_void_p
-        L.owo_engine_new_kind.restype = C.c_void_p
-        L.owo_engine_new_kinds.restype = C.c_void_p
-        L.owo_engine_new_kinds3.restype = C.c_void_p
-        for name in ("owo_midi_to_freq", "owo_tip_mass_ratio", "owo_reed_length_mm", "owo_pickup_displacement_scale",
-                     "owo_fundamental_decay_rate", "owo_output_scale", "owo_velocity_exponent", "owo_velocity_scurve",
-                     "owo_register_trim_db", "owo_pickup_rms_proxy", "owo_freq_detune", "owo_dwell_time", "owo_onset_ramp_time",
-                     "owo_pickup_soft_saturate", "owo_fast_exp", "owo_power_amp", "owo_alias_dft_magnitude", "owo_alias_bandpass_rms",
-                     "owo_alias_plateau_metric", "owo_mode_shape", "owo_reed_compliance"):
-            getattr(L, name).restype = C.c_double
-        L.owo_render_note.restype = C.c_size_t
-        L.owo_batch_render_job.restype = C.c_size_t
-        L.owo_batch_render_job_kind.restype = C.c_size_t
-        L.owo_engine_nan_guard_fires.restype = C.c_ulonglong
-        L.owo_alias_audit_render_stimulus.restype = C.c_size_t
-        L.owo_alias_audit_result_size.restype = C.c_size_t
-    return L
+    """All three libraries at once (build.sh); lib*() below ask make for their own."""
+    subprocess.check_call(["make", "-s", "-C", native.ORACLE_DIR])
 
 
 def lib():
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(_PATH):
-            build()
-        _LIB = _configure(C.CDLL(_PATH))
-    return _LIB
+    return native.load("ow_oracle")
 
 
 def lib_perturbed():
     """Sensitivity variant of the oracle (BJT exp() off by one ulp, oracle/ow_chain.hpp)."""
-    global _LIB_P
-    if _LIB_P is None:
-        if not os.path.exists(_PATH_PERTURBED):
-            build()
-        _LIB_P = _configure(C.CDLL(_PATH_PERTURBED))
-    return _LIB_P
-
-
-_PATH_VOICE_PERTURBED = os.path.join(_ROOT, "oracle", "_build", "libow_oracle_voice_perturbed.so")
-_LIB_V = None
+    return native.load("ow_oracle", "perturbed")
 
 
 def lib_voice_perturbed():
     """Second sensitivity variant: the voice path's rotation / decay library calls off by one ulp (oracle/ow_voice.hpp)."""
-    global _LIB_V
-    if _LIB_V is None:
-        if not os.path.exists(_PATH_VOICE_PERTURBED):
-            build()
-        _LIB_V = _configure(C.CDLL(_PATH_VOICE_PERTURBED))
-    return _LIB_V
+    return native.load("ow_oracle", "voice_perturbed")
 
 
 def _p(a):
@@ -83,7 +39,7 @@ class OracleEngine:
 
     def __init__(self, sr, perturbed=False, preamp_kind=0, power_amp_kind=0, tremolo_kind=0):
         self.L = lib_voice_perturbed() if perturbed == "voice" else (lib_perturbed() if perturbed else lib())
-        self.h = C.c_void_p(self.L.owo_engine_new_kinds3(C.c_double(sr), int(preamp_kind), int(power_amp_kind), int(tremolo_kind)))
+        self.h = C.c_void_p(self.L.owo_engine_new_kinds3(sr, int(preamp_kind), int(power_amp_kind), int(tremolo_kind)))
 
     def close(self):
         if self.h:
@@ -93,29 +49,29 @@ class OracleEngine:
     def __del__(self):
         self.close()
 
-    def set_sample_rate(self, sr): self.L.owo_engine_set_sample_rate(self.h, C.c_double(sr))
+    def set_sample_rate(self, sr): self.L.owo_engine_set_sample_rate(self.h, sr)
     def reset(self): self.L.owo_engine_reset(self.h)
     def warm_up(self): self.L.owo_engine_warm_up(self.h)
-    def note_on(self, n, v): self.L.owo_engine_note_on(self.h, int(n), C.c_float(v))
+    def note_on(self, n, v): self.L.owo_engine_note_on(self.h, int(n), v)
     def note_off(self, n): self.L.owo_engine_note_off(self.h, int(n))
     def set_sustain(self, h): self.L.owo_engine_set_sustain(self.h, 1 if h else 0)
-    def set_volume(self, v): self.L.owo_engine_set_volume(self.h, C.c_double(v))
-    def set_tremolo_depth(self, v): self.L.owo_engine_set_tremolo_depth(self.h, C.c_double(v))
-    def set_speaker_character(self, v): self.L.owo_engine_set_speaker_character(self.h, C.c_double(v))
+    def set_volume(self, v): self.L.owo_engine_set_volume(self.h, v)
+    def set_tremolo_depth(self, v): self.L.owo_engine_set_tremolo_depth(self.h, v)
+    def set_speaker_character(self, v): self.L.owo_engine_set_speaker_character(self.h, v)
     def set_mlp_enabled(self, on): self.L.owo_engine_set_mlp_enabled(self.h, 1 if on else 0)
     def set_noise_enabled(self, on): self.L.owo_engine_set_noise_enabled(self.h, 1 if on else 0)
-    def set_noise_gain(self, g): self.L.owo_engine_set_noise_gain(self.h, C.c_double(g))
-    def set_noise_seed(self, seed): self.L.owo_engine_set_noise_seed(self.h, C.c_ulonglong(int(seed)))
+    def set_noise_gain(self, g): self.L.owo_engine_set_noise_gain(self.h, g)
+    def set_noise_seed(self, seed): self.L.owo_engine_set_noise_seed(self.h, int(seed))
 
     def render(self, n):
         out = np.zeros(int(n), dtype=np.float32)
-        self.L.owo_engine_render(self.h, _p(out), C.c_size_t(int(n)))
+        self.L.owo_engine_render(self.h, _p(out), int(n))
         return out
 
     def render_tap(self, n):
         out = np.zeros(int(n), dtype=np.float32)
         vs = np.zeros(int(n), dtype=np.float64)
-        self.L.owo_engine_render_tap(self.h, _p(out), _p(vs), C.c_size_t(int(n)))
+        self.L.owo_engine_render_tap(self.h, _p(out), _p(vs), int(n))
         return out, vs
 
     def render_taps(self, n, osr=2):
@@ -123,7 +79,7 @@ class OracleEngine:
         vs = np.zeros(int(n), dtype=np.float64)
         pre = np.zeros(int(n) * osr, dtype=np.float64)
         r = np.zeros(int(n) * osr, dtype=np.float64)
-        self.L.owo_engine_render_taps(self.h, _p(out), _p(vs), _p(pre), _p(r), C.c_size_t(int(n)))
+        self.L.owo_engine_render_taps(self.h, _p(out), _p(vs), _p(pre), _p(r), int(n))
         return out, vs, pre, r
 
     def set_rail_sag(self, on): self.L.owo_engine_set_rail_sag(self.h, 1 if on else 0)
@@ -139,18 +95,18 @@ class OracleEngine:
     def render_pa_tap(self, n, osr=2):
         out = np.zeros(int(n), dtype=np.float32)
         pa = np.zeros(int(n) * osr, dtype=np.float64)
-        self.L.owo_engine_render_pa_tap(self.h, _p(out), _p(pa), C.c_size_t(int(n)))
+        self.L.owo_engine_render_pa_tap(self.h, _p(out), _p(pa), int(n))
         return out, pa
 
-    def advance_tremolo(self, n): self.L.owo_engine_advance_tremolo(self.h, C.c_size_t(int(n)))
+    def advance_tremolo(self, n): self.L.owo_engine_advance_tremolo(self.h, int(n))
 
     def poke_voice(self, slot, steal, field, value):
         """test poke: field 81 = pickup charge q, 0 = mode 0's sine state (the product's ow_test_engine_poke_voice)"""
-        return self.L.owo_engine_poke_voice(self.h, int(slot), 1 if steal else 0, int(field), C.c_double(value))
+        return self.L.owo_engine_poke_voice(self.h, int(slot), 1 if steal else 0, int(field), value)
 
     def poke_preamp_node(self, node, volts, shadow=False):
         """test poke: a node voltage of the legacy preamp's solver state (the product's ow_test_engine_poke_preamp_node)"""
-        self.L.owo_engine_poke_preamp_node(self.h, 1 if shadow else 0, int(node), C.c_double(volts))
+        self.L.owo_engine_poke_preamp_node(self.h, 1 if shadow else 0, int(node), volts)
 
     def preamp_state(self, shadow=False):
         """the legacy preamp's solver state as stored (j_cin, cin_rhs_prev, v[8], i_nl[2], v_nl[2]) + bjt_ic(v_nl[0..1]) evaluated now"""
@@ -168,7 +124,7 @@ class OracleEngine:
         """test instrumentation: the tremolo's r_ldr moved by `ulps` doubles from now on (another libm's pow / exp / sin)"""
         self.L.owo_engine_set_r_ulp(self.h, int(ulps))
 
-    def poke_power_amp_node(self, node, volts): self.L.owo_engine_poke_pa_node(self.h, int(node), C.c_double(volts))
+    def poke_power_amp_node(self, node, volts): self.L.owo_engine_poke_pa_node(self.h, int(node), volts)
 
     def stage_rows(self):
         """the output stage's state as the product's chain-state rows (float64 [STAGE_ROW_COUNT], CS_* indices; the rest 0)"""
@@ -225,8 +181,8 @@ def output_stage_block(host_rate, rows_in, tap, n, set_flags=0, spk_target=0.0, 
     pert = None
     if pattern is not None:
         pert = np.array(list(ulps) + [STAGE_PATTERNS[pattern], int(seed)], dtype=np.int32)
-    rc = lib().owo_output_stage_block(C.c_double(host_rate), osr, int(amp_kind), _p(rows_in), C.c_uint(int(set_flags)), C.c_double(spk_target),
-                                      C.c_double(vol_target), _p(tap), C.c_size_t(n), _p(rows_out), _p(out), _p(info),
+    rc = lib().owo_output_stage_block(host_rate, osr, int(amp_kind), _p(rows_in), int(set_flags), spk_target,
+                                      vol_target, _p(tap), n, _p(rows_out), _p(out), _p(info),
                                       None if pert is None else _p(pert), int(STAGE_MUTANTS[mutant]), _p(out64))
     assert rc == 0, rc
     m = n * osr
@@ -245,7 +201,7 @@ def dk_step_cases(rate, states, inputs, g_ldr, g_ldr_prev, perturbed=False):
     gp = np.ascontiguousarray(g_ldr_prev, dtype=np.float64)
     assert x.shape == (n,) and g.shape == (n,) and gp.shape == (n,)
     so = np.zeros((n, 14)); out = np.zeros(n); info = np.zeros((n, 4), dtype=np.int32)
-    L.owo_dk_step_cases(C.c_double(rate), _p(st), _p(x), _p(g), _p(gp), C.c_size_t(n), _p(so), _p(out), _p(info))
+    L.owo_dk_step_cases(rate, _p(st), _p(x), _p(g), _p(gp), n, _p(so), _p(out), _p(info))
     return so, out, info
 
 
@@ -262,7 +218,7 @@ def trem_step_cases(rate, states, log_ulp=0):
     n = st.shape[0]
     assert st.shape == (n, 15)
     so = np.zeros((n, 15)); out = np.zeros(n); info = np.zeros((n, 10), dtype=np.int32)
-    lib().owo_trem_step_cases(C.c_double(rate), _p(st), C.c_size_t(n), C.c_int(int(log_ulp)), _p(so), _p(out), _p(info))
+    lib().owo_trem_step_cases(rate, _p(st), n, int(log_ulp), _p(so), _p(out), _p(info))
     return so, out, info
 
 
@@ -272,7 +228,7 @@ def trem_harvest(rate, n, every, state=None):
     m = (int(n) + int(every) - 1) // int(every)
     out = np.zeros((m, 15))
     st = None if state is None else _p(np.ascontiguousarray(state, dtype=np.float64))
-    lib().owo_trem_harvest(C.c_double(rate), st, C.c_size_t(int(n)), C.c_size_t(int(every)), _p(out))
+    lib().owo_trem_harvest(rate, st, int(n), int(every), _p(out))
     return out
 
 
@@ -295,9 +251,9 @@ def melange_step_cases(rate, states, inputs, r_ldr, log_ulp=0, r_ulp=0, rebuilt=
     so = np.zeros((n, 21)); out = np.zeros(n); info = np.zeros((n, 14), dtype=np.int32)
     if rebuilt:
         assert log_ulp == 0 and r_ulp == 0
-        lib().owo_melange_step_cases_rebuilt(C.c_double(rate), _p(st), _p(x), _p(r), C.c_size_t(n), _p(so), _p(out), _p(info))
+        lib().owo_melange_step_cases_rebuilt(rate, _p(st), _p(x), _p(r), n, _p(so), _p(out), _p(info))
         return so, out, info
-    lib().owo_melange_step_cases(C.c_double(rate), _p(st), _p(x), _p(r), C.c_size_t(n), C.c_int(int(log_ulp)), C.c_int(int(r_ulp)), _p(so), _p(out), _p(info))
+    lib().owo_melange_step_cases(rate, _p(st), _p(x), _p(r), n, int(log_ulp), int(r_ulp), _p(so), _p(out), _p(info))
     return so, out, info
 
 
@@ -309,21 +265,21 @@ def melange_harvest(rate, n, every, x=None, r=None):
     xx = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
     rr = None if r is None else np.ascontiguousarray(r, dtype=np.float64)
     assert (xx is None or xx.shape == (n,)) and (rr is None or rr.shape == (n,))
-    lib().owo_melange_harvest(C.c_double(rate), None if xx is None else _p(xx), None if rr is None else _p(rr), C.c_size_t(n), C.c_size_t(every), _p(out), _p(y))
+    lib().owo_melange_harvest(rate, None if xx is None else _p(xx), None if rr is None else _p(rr), n, every, _p(out), _p(y))
     return out, y
 
 
 def preamp_dc_nodes(rate, r_ldr):
     """The eight node voltages of the legacy preamp after set_ldr_resistance(r_ldr); reset() at chain rate `rate` (full_dc_solve at that R)."""
     v = np.zeros(8)
-    lib().owo_preamp_step(C.c_double(rate), C.c_double(r_ldr), C.c_size_t(0), C.c_double(r_ldr), None, None, C.c_size_t(0), _p(v))
+    lib().owo_preamp_step(rate, r_ldr, 0, r_ldr, None, None, 0, _p(v))
     return v
 
 
 def render_note(midi, vel, dur, sr):
     n = int(dur * sr)
     out = np.zeros(max(n, 1))
-    got = lib().owo_render_note(int(midi), C.c_double(vel), C.c_double(dur), C.c_double(sr), _p(out), C.c_size_t(out.size))
+    got = lib().owo_render_note(int(midi), vel, dur, sr, _p(out), out.size)
     return out[:got]
 
 
@@ -331,8 +287,8 @@ def batch_render_job(note, vel_u8, dur, sr, volume=1.0, speaker=0.0, r_ldr=1e6, 
     n = int(dur * sr)
     out = np.zeros(max(n, 1))
     got = (lib_perturbed() if perturbed else lib()).owo_batch_render_job_kind(
-        int(note), int(vel_u8), C.c_double(dur), C.c_double(sr), C.c_double(volume), C.c_double(speaker), C.c_double(r_ldr),
-        1 if mlp else 0, 1 if poweramp else 0, int(preamp_kind), _p(out), C.c_size_t(out.size))
+        int(note), int(vel_u8), dur, sr, volume, speaker, r_ldr,
+        1 if mlp else 0, 1 if poweramp else 0, int(preamp_kind), _p(out), out.size)
     return out[:got]
 
 
@@ -340,42 +296,38 @@ def batch_render_job_ex(note, vel_u8, dur, sr, volume=0.60, speaker=1.0, r_ldr=1
                         poweramp=True, no_preamp=False, no_attack_noise=False, no_rail_sag=False, preamp_kind=0, power_amp_kind=0):
     """`preamp-bench render` with every sample-changing flag (tools/preamp-bench/src/main.rs:371-549); defaults = the command's."""
     L = lib()
-    L.owo_batch_render_job_ex.restype = C.c_size_t
     n = int(dur * sr)
     out = np.zeros(max(n, 1))
     opts = np.array([volume, speaker, r_ldr, tremolo_depth, float("nan") if displacement_scale is None else displacement_scale])
     flags = (1 if mlp else 0) | (2 if poweramp else 0) | (4 if no_preamp else 0) | (8 if no_attack_noise else 0) | (16 if no_rail_sag else 0)
-    got = L.owo_batch_render_job_ex(int(note), int(vel_u8), C.c_double(dur), C.c_double(sr), _p(opts), C.c_uint(flags), int(preamp_kind),
-                                    int(power_amp_kind), _p(out), C.c_size_t(out.size))
+    got = L.owo_batch_render_job_ex(int(note), int(vel_u8), dur, sr, _p(opts), flags, int(preamp_kind),
+                                    int(power_amp_kind), _p(out), out.size)
     return out[:got]
 
 
 def render_note_scaled(midi, vel, dur, sr, scale):
     L = lib()
-    L.owo_render_note_scaled.restype = C.c_size_t
     n = int(dur * sr)
     out = np.zeros(max(n, 1))
-    got = L.owo_render_note_scaled(int(midi), C.c_double(vel), C.c_double(dur), C.c_double(sr), C.c_double(scale), _p(out), C.c_size_t(out.size))
+    got = L.owo_render_note_scaled(int(midi), vel, dur, sr, scale, _p(out), out.size)
     return out[:got]
 
 
 def render_midi_ex(time_s, types, notes, values, volume=0.6, speaker=1.0, no_poweramp=False, tail=2.0, preamp_kind=0, power_amp_kind=0, no_rail_sag=False):
     L = lib()
-    L.owo_render_midi_ex.restype = C.c_size_t
     t = np.ascontiguousarray(time_s, dtype=np.float64); ty = np.ascontiguousarray(types, dtype=np.uint8)
     no = np.ascontiguousarray(notes, dtype=np.uint8); va = np.ascontiguousarray(values, dtype=np.uint8)
     cap = int((float(t.max()) + tail) * 44100.0) + 16 if t.size else 1
     out = np.zeros(cap)
-    got = L.owo_render_midi_ex(_p(t), _p(ty), _p(no), _p(va), C.c_size_t(t.size), C.c_double(volume), C.c_double(speaker), 1 if no_poweramp else 0,
-                               C.c_double(tail), int(preamp_kind), int(power_amp_kind), 1 if no_rail_sag else 0, _p(out), C.c_size_t(cap))
+    got = L.owo_render_midi_ex(_p(t), _p(ty), _p(no), _p(va), t.size, volume, speaker, 1 if no_poweramp else 0,
+                               tail, int(preamp_kind), int(power_amp_kind), 1 if no_rail_sag else 0, _p(out), cap)
     return out[:got]
 
 
 def normalize_scale(x):
     L = lib()
-    L.owo_batch_normalize_scale.restype = C.c_double
     x = np.ascontiguousarray(x, dtype=np.float64)
-    return L.owo_batch_normalize_scale(_p(x), C.c_size_t(x.size))
+    return L.owo_batch_normalize_scale(_p(x), x.size)
 
 
 class AliasAuditResult(C.Structure):
@@ -386,7 +338,7 @@ class AliasAuditResult(C.Structure):
 
 def alias_audit_render_stimulus(note, velocity, preamp_kind=0, perturbed=False):
     out = np.zeros(int(44100.0 * 1.5))
-    got = (lib_perturbed() if perturbed else lib()).owo_alias_audit_render_stimulus(int(note), int(velocity), int(preamp_kind), _p(out), C.c_size_t(out.size))
+    got = (lib_perturbed() if perturbed else lib()).owo_alias_audit_render_stimulus(int(note), int(velocity), int(preamp_kind), _p(out), out.size)
     assert got == out.size
     return out
 
@@ -395,7 +347,7 @@ def alias_audit_analyze(signal, sr, nominal_f0):
     assert lib().owo_alias_audit_result_size() == C.sizeof(AliasAuditResult)
     signal = np.ascontiguousarray(signal, dtype=np.float64)
     r = AliasAuditResult()
-    rc = lib().owo_alias_audit_analyze(_p(signal), C.c_size_t(signal.size), C.c_double(sr), C.c_double(nominal_f0), C.byref(r))
+    rc = lib().owo_alias_audit_analyze(_p(signal), signal.size, sr, nominal_f0, C.byref(r))
     if rc != 0:
         raise ValueError("alias_audit signal too short")
     return r

@@ -1,45 +1,24 @@
 """ctypes loader of the CPU restatement of `preamp-bench gain` / `sweep` / `harmonics` / `tremolo-sweep` (tests/c/preamp_bench_ref.cpp,
 over the oracle's headers).
 
-It is compiled on first use with the oracle Makefile's flags into a temporary directory; nothing of it is kept in the tree.  Every function
-returns per point the nine values the restatement computes: gain, gain_db, H1..H5, THD %, H2/H3 dB (MET fields).
+tests/native.py has oracle/Makefile build it into oracle/_build when it is out of date, and declares its functions from that source.  Every
+function returns per point the nine values the restatement computes: gain, gain_db, H1..H5, THD %, H2/H3 dB (MET fields).
 """
 import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]      # oracle/Makefile
+import native
+
 N_SAMPLES = 22050
 MET = ("gain", "gain_db", "h1", "h2", "h3", "h4", "h5", "thd_pct", "h2_h3_db")
-_LIB = None
-_LOCK = threading.Lock()
 _WARM = set()
-_VP, _D = C.c_void_p, C.c_double
+_VP = C.c_void_p
 
 
 def lib():
-    global _LIB
-    with _LOCK:
-        if _LIB is None:
-            out = os.path.join(tempfile.mkdtemp(prefix="pbref_"), "libpreamp_bench_ref.so")
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + ["-shared", "-I", os.path.join(ROOT, "oracle"), "-o", out,
-                                                                          os.path.join(HERE, "c", "preamp_bench_ref.cpp"), "-lm"])
-            L = C.CDLL(out)
-            L.opb_measure_seq.restype = None
-            L.opb_measure_seq.argtypes = [C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP]
-            L.opb_harmonics.restype = None
-            L.opb_harmonics.argtypes = [C.c_int, _D, _D, _D, _VP, _VP]
-            L.opb_point.restype = None
-            L.opb_point.argtypes = [C.c_int, _D, _D, _D, _D, _VP, _VP]
-            _LIB = L
-    return _LIB
+    return native.load("preamp_bench_ref")
 
 
 def _p(a):

@@ -1,26 +1,18 @@
-"""ctypes loader of the CPU restatement of the pump measurements (tests/c/pump_ref.cpp, over oracle/ow_melange.hpp).  It is compiled on first
-use with the oracle Makefile's flags into a temporary directory; nothing of it is kept in the tree.
+"""ctypes loader of the CPU restatement of the pump measurements (tests/c/pump_ref.cpp, over oracle/ow_melange.hpp).  tests/native.py has
+oracle/Makefile build it into oracle/_build when it is out of date, and declares its functions from that source.
 
 Also here, because the host and the GPU tests share them: the points the GPU tests run, the restatement's own one-ulp movement at those
 points (measured by tests/test_pump_host.py, which holds the restatement to 2.5 x these figures), and the device's parity bar.
 """
 import ctypes as C
 import math
-import os
-import subprocess
-import tempfile
-import threading
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+import native
 from openwurli_amd import pump
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]      # oracle/Makefile
-_LIB = None
-_LOCK = threading.Lock()
 _VP = C.c_void_p
 
 # The restatement's own movement when every non-zero entry of the rebuilt s, k, s_ni moves by one ulp (both polarities), largest
@@ -72,19 +64,7 @@ def placement_points() -> np.ndarray:
 
 
 def lib():
-    global _LIB
-    with _LOCK:
-        if _LIB is None:
-            out = os.path.join(tempfile.mkdtemp(prefix="pumpref_"), "libpump_ref.so")
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + ["-shared", "-I", os.path.join(ROOT, "oracle"), "-o", out,
-                                                                                os.path.join(HERE, "c", "pump_ref.cpp"), "-lm"])
-            L = C.CDLL(out)
-            L.opr_run.restype, L.opr_run.argtypes = C.c_int, [_VP, C.c_int, _VP, _VP]
-            L.opr_trace_stats.restype, L.opr_trace_stats.argtypes = None, [_VP, C.c_size_t, _VP]
-            L.opr_step_tail.restype, L.opr_step_tail.argtypes = None, [_VP, C.c_size_t, _VP]
-            L.opr_sinusoid_bifurcs.restype, L.opr_sinusoid_bifurcs.argtypes = C.c_size_t, [_VP, C.c_size_t]
-            _LIB = L
-    return _LIB
+    return native.load("pump_ref")
 
 
 def run_point(point, polarity=0, trace=True):

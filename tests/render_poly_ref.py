@@ -1,31 +1,24 @@
 """ctypes loader of the CPU restatement of `preamp-bench render-poly` (tests/c/render_poly_ref.cpp, over the oracle's headers).
 
-It is compiled on first use with the oracle Makefile's flags into a temporary directory; nothing of it is kept in the tree.  A second build
-with -DOW_ORACLE_EXP_PERTURB (the BJT exp() off by one ulp, oracle/ow_chain.hpp) is the sensitivity variant the sample floor is measured
-with.  render() returns a Result: the row figures (ROW fields, include/openwurli_hip.h ow_poly_row), final, separate_sum, residual and the
-per-voice rows -- the outputs of the voices' OWN chains, i.e. the terms of separate_sum.
+tests/native.py has oracle/Makefile build it into oracle/_build when it is out of date, and declares its functions from that source.  A
+second build with -DOW_ORACLE_EXP_PERTURB (the BJT exp() off by one ulp, oracle/ow_chain.hpp) is the sensitivity variant the sample floor is
+measured with.  render() returns a Result: the row figures (ROW fields, include/openwurli_hip.h ow_poly_row), final, separate_sum, residual
+and the per-voice rows -- the outputs of the voices' OWN chains, i.e. the terms of separate_sum.
 
 Also here, because both the host and the GPU tests use them: the chords the GPU parity test runs (CHORDS), the sample bars of the three
 outputs, and the condition that keeps an assertion on intermod_ratio_db honest.
 """
 import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
 from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"]      # oracle/Makefile
+import native
+
 ROW = ("peak", "residual_peak", "win_peak", "win_mean_sq", "peak_db", "rms_db", "intermod_ratio_db")
 WIN_LO, WIN_HI = 8820, 88200                                                           # main.rs:1516-1517
-_LIBS = {}
-_LOCK = threading.Lock()
-_VP, _D = C.c_void_p, C.c_double
+_VP = C.c_void_p
 
 Result = namedtuple("Result", "row final separate_sum residual voices")
 Chord = namedtuple("Chord", "notes velocities duration volume speaker ldr no_poweramp")
@@ -48,18 +41,7 @@ ABS_FLOOR_POLY = 2.3e-8
 
 
 def lib(perturbed=False):
-    with _LOCK:
-        if perturbed not in _LIBS:
-            out = os.path.join(tempfile.mkdtemp(prefix="rpref_"), "librender_poly_ref%s.so" % ("_perturbed" if perturbed else ""))
-            subprocess.check_call([os.environ.get("CXX", "g++")] + CXXFLAGS + (["-DOW_ORACLE_EXP_PERTURB"] if perturbed else []) +
-                                  ["-shared", "-I", os.path.join(ROOT, "oracle"), "-o", out, os.path.join(HERE, "c", "render_poly_ref.cpp"), "-lm"])
-            L = C.CDLL(out)
-            L.orp_samples.restype = C.c_size_t
-            L.orp_samples.argtypes = [_D]
-            L.orp_render.restype = C.c_size_t
-            L.orp_render.argtypes = [C.c_int, _VP, _VP, _D, _D, _D, _D, C.c_int, _VP, _VP, _VP, _VP, _VP]
-            _LIBS[perturbed] = L
-    return _LIBS[perturbed]
+    return native.load("render_poly_ref", "perturbed" if perturbed else "")
 
 
 def samples(duration):

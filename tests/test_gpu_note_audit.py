@@ -286,8 +286,6 @@ def test_note_table_against_the_oracle(hiplib, oracle):
     assert hiplib.ow_debug_note_table(nt.ctypes.data_as(C.c_void_p), 0) == 0, hiplib.ow_last_error()
     L = oracle.lib()
     d = C.c_double
-    for f in ("owo_midi_to_freq", "owo_tip_mass_ratio", "owo_reed_length_mm"):
-        getattr(L, f).restype = d
     base = (1.0, 0.005, 0.0035, 0.0018, 0.0011, 0.0007, 0.0005)
     worst_f0 = worst_amp = worst_share = 0.0
     for ni in range(64):

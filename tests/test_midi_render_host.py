@@ -19,7 +19,6 @@ TRACKS = [
 
 def _oracle_parse(oracle, data, track_filter):
     L = oracle.lib()
-    L.owo_smf_parse.restype = C.c_longlong
     buf = np.frombuffer(data, dtype=np.uint8)
     cap = 256
     t = np.zeros(cap); ty = np.zeros(cap, np.uint8); no = np.zeros(cap, np.uint8); va = np.zeros(cap, np.uint8)
@@ -90,7 +89,6 @@ def test_render_length_rules_need_no_device(hiplib_host):
 
 def _oracle_render(oracle, items, volume=0.6, speaker=1.0, no_pa=False, tail=2.0):
     L = oracle.lib()
-    L.owo_render_midi.restype = C.c_size_t
     t = np.array([x[0] for x in items], dtype=np.float64); ty = np.array([x[1] for x in items], dtype=np.uint8)
     no = np.array([x[2] for x in items], dtype=np.uint8); va = np.array([x[3] for x in items], dtype=np.uint8)
     cap = int((max(x[0] for x in items) + tail) * 44100.0) + 8 if items else 8

@@ -292,8 +292,7 @@ def test_power_amp_dc_operating_point(oracle):
     full = root(lambda v: kcl(v, True), v0, tol=1e-13)
     assert full.success and np.max(np.abs(kcl(full.x, True))) < 1e-10
     assert 7.0e-3 < np.max(np.abs(full.x - v0)) < 7.6e-3                                           # (3) the runtime rest point, 7.27 mV off DC_OP
-    L.owo_mpa_new.restype = C.c_void_p
-    h = C.c_void_p(L.owo_mpa_new(C.c_double(fs)))
+    h = C.c_void_p(L.owo_mpa_new(fs))
     L.owo_mpa_set_rail_sag(h, 0)
     x = np.zeros(int(fs) * 3); y = np.zeros_like(x)
     L.owo_mpa_process(h, _p(x), _p(y), None, C.c_size_t(len(x)))

@@ -17,8 +17,7 @@ DC_OP_JSON = ("[0.0, 3.83906281848339984e-2, 6.54729553363387007e-1, 2.250000000
 class Mpa:
     def __init__(self, L, sr=SR):
         self.L = L
-        L.owo_mpa_new.restype = C.c_void_p
-        self.h = C.c_void_p(L.owo_mpa_new(C.c_double(sr)))
+        self.h = C.c_void_p(L.owo_mpa_new(sr))
 
     def close(self):
         self.L.owo_mpa_free(self.h)

@@ -35,9 +35,7 @@ def test_render_note_agrees_with_the_cpp_oracle_over_one_second(midi, vel):
 def test_note_on_parameters_agree_field_by_field():
     """Voice::note_on's outputs (phase increments, amplitudes after spatial coupling / dwell / +-8 % / velocity curve, decay multipliers,
     onset ramp, displacement scale, post-pickup gain) against the oracle's packed block (owo_voice_params), to the last bit."""
-    import ctypes as C
     L = ob.lib()
-    L.owo_voice_params.argtypes = [C.c_int, C.c_double, C.c_double, C.c_uint, C.c_int, C.c_void_p]
     for midi, vel in CASES + [(45, 0.62), (72, 0.05), (84, 0.999)]:
         out = np.zeros(64)
         L.owo_voice_params(midi, vel, SR, (midi * 2654435761) & 0xFFFFFFFF, 0, out.ctypes.data)
