@@ -179,6 +179,53 @@ int ow_test_engine_read_preamp_state(ow_engine*, int shadow, double* out14);
 int ow_test_engine_read_chain_rows(ow_engine*, int first_row, int n_rows, double* out);
 int ow_test_engine_write_chain_rows(ow_engine*, int first_row, int n_rows, const double* in);
 
+/* ---- voice records -------------------------------------------------------------------------------- */
+/* One voice record (VF_* of openwurli_amd/csrc/ow_types.h) copied out to / in from OW_TEST_VF_COUNT doubles, field-major: out[f] is field
+ * f of the voice in `slot` (steal != 0: the slot's steal voice); on the device the fields lie 64 doubles apart.  u64 fields travel as
+ * their bits: SAMPLE and ONSET_N whole; RNG = jitter_state | noise rng << 32; NCNT = noise remaining | fade-in remaining << 32; FLAGS =
+ * (bit 0 damper active, bit 1 ramp done) | midi note << 32; STEAL (steal records only) = steal_fade | steal_fade_len << 32.  The mode
+ * fields are seven wide (a name ending in 0 is mode 0's).  A voice block -- k_voice, k_voice_steady and its skewed, attack, steal and release variants
+ * -- is a pure function (record, L) -> (record, L samples at the voice-sum tap, status bits), which tests/test_gpu_voice_block.py compares
+ * with the oracle's (owo_voice_block).  The read waits for the stream and shows the records as the last render left them (ops queued
+ * since are applied by the next render).  The write forgets a block rendered ahead, has the voice lists packed again and re-derives the
+ * engine's transient flag -- which voice kernel its slot voices get -- from the records of its sounding slot voices as they then stand
+ * (damper bit, sample < onset_n, noise remaining); which slots are occupied, releasing or stolen stays what the API calls made it.
+ * Return 0, <0 on error. */
+#define OW_TEST_VF_C0 7
+#define OW_TEST_VF_ENV0 14
+#define OW_TEST_VF_DRIFT0 21
+#define OW_TEST_VF_COS_INC0 28
+#define OW_TEST_VF_SIN_INC0 35
+#define OW_TEST_VF_PHASE_INC0 42
+#define OW_TEST_VF_AMP0 49
+#define OW_TEST_VF_DECAY0 56
+#define OW_TEST_VF_DRATE0 63
+#define OW_TEST_VF_DMULT0 70
+#define OW_TEST_VF_ONSET_INC 77
+#define OW_TEST_VF_ONSET_EXP 78
+#define OW_TEST_VF_DRAMP 79
+#define OW_TEST_VF_DCOUNT 80
+#define OW_TEST_VF_DS 82
+#define OW_TEST_VF_GAIN 83
+#define OW_TEST_VF_NAMP 84
+#define OW_TEST_VF_NB0 85      /* [5] attack-noise band-pass b0 b1 b2 a1 a2 */
+#define OW_TEST_VF_NS1 90
+#define OW_TEST_VF_NS2 91
+#define OW_TEST_VF_SAMPLE 92
+#define OW_TEST_VF_ONSET_N 93
+#define OW_TEST_VF_RNG 94
+#define OW_TEST_VF_NCNT 95
+#define OW_TEST_VF_FLAGS 96
+#define OW_TEST_VF_STEAL 97
+#define OW_TEST_VF_BETA 98
+#define OW_TEST_VF_JREV 99
+#define OW_TEST_VF_JDIFF 100
+#define OW_TEST_VF_NDECAY 101
+#define OW_TEST_VF_VSR 102
+#define OW_TEST_VF_COUNT 103
+int ow_test_engine_read_voice_record(ow_engine*, int slot, int steal, double* out);
+int ow_test_engine_write_voice_record(ow_engine*, int slot, int steal, const double* in);
+
 /* Plain device-to-host copy, for reading a block that ow_pool_render(pool, NULL, ...) left in HBM (ow_pool_device_output). */
 int ow_test_device_read(void* dst_host, const void* src_device, size_t bytes, int device);
 /* Plain host-to-device copy into a buffer of ow_device_alloc, for handing given audio to an entry point's audio_is_device path. */

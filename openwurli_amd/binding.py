@@ -439,6 +439,8 @@ SYMBOLS = {
 }
 
 
+VOICE_RECORD_FIELDS = 103     # OW_TEST_VF_COUNT: doubles of one voice record (ow_test_engine_read_voice_record / _write_voice_record)
+
 # include/openwurli_hip_test.h: test and debug hooks (not part of the drop-in boundary; bound for tests/ only)
 TEST_SYMBOLS = {
     "ow_test_engine_new": (_VP, [C.c_double]),
@@ -480,6 +482,8 @@ TEST_SYMBOLS = {
     "ow_test_engine_read_preamp_state": (C.c_int, [_VP, C.c_int, _VP]),
     "ow_test_engine_read_chain_rows": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
     "ow_test_engine_write_chain_rows": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
+    "ow_test_engine_read_voice_record": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
+    "ow_test_engine_write_voice_record": (C.c_int, [_VP, C.c_int, C.c_int, _VP]),
     "ow_test_host_matrices": (C.c_int, [C.c_int, C.c_double, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "ow_debug_trem_trajectory": (C.c_int, [C.c_double, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int, _VP, _VP]),
 }

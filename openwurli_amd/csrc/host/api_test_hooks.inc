@@ -245,6 +245,56 @@ int ow_test_engine_write_chain_rows(ow_engine* e, int first_row, int n_rows, con
     double* dst = p->d_cs + (size_t)first_row * p->I + e->index;
     return hipMemcpy2D(dst, sizeof(double) * p->I, in, sizeof(double), sizeof(double), (size_t)n_rows, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
 }
+// One whole voice record, vrec[e][steal][field][slot], copied out / in field-major (out[f] = field f of that slot; u64 fields as their
+// bits): a voice block is a pure function (record, L) -> (record, L samples, status bits), and this is how a test starts it from any record
+// and reads what it left.  The read shows the record as the last render left it: ops queued since are applied by the next one.
+static_assert(VF_S == OW_TEST_VF_S0 && VF_C == OW_TEST_VF_C0 && VF_ENV == OW_TEST_VF_ENV0 && VF_DRIFT == OW_TEST_VF_DRIFT0 &&
+              VF_COS_INC == OW_TEST_VF_COS_INC0 && VF_SIN_INC == OW_TEST_VF_SIN_INC0 && VF_PHASE_INC == OW_TEST_VF_PHASE_INC0 &&
+              VF_AMP == OW_TEST_VF_AMP0 && VF_DECAY == OW_TEST_VF_DECAY0 && VF_DRATE == OW_TEST_VF_DRATE0 && VF_DMULT == OW_TEST_VF_DMULT0 &&
+              VF_ONSET_INC == OW_TEST_VF_ONSET_INC && VF_ONSET_EXP == OW_TEST_VF_ONSET_EXP && VF_DRAMP == OW_TEST_VF_DRAMP &&
+              VF_DCOUNT == OW_TEST_VF_DCOUNT && VF_Q == OW_TEST_VF_Q && VF_DS == OW_TEST_VF_DS && VF_GAIN == OW_TEST_VF_GAIN &&
+              VF_NAMP == OW_TEST_VF_NAMP && VF_NB0 == OW_TEST_VF_NB0 && VF_NA2 == OW_TEST_VF_NB0 + 4 && VF_NS1 == OW_TEST_VF_NS1 &&
+              VF_NS2 == OW_TEST_VF_NS2 && VF_SAMPLE == OW_TEST_VF_SAMPLE && VF_ONSET_N == OW_TEST_VF_ONSET_N && VF_RNG == OW_TEST_VF_RNG &&
+              VF_NCNT == OW_TEST_VF_NCNT && VF_FLAGS == OW_TEST_VF_FLAGS && VF_STEAL == OW_TEST_VF_STEAL && VF_BETA == OW_TEST_VF_BETA &&
+              VF_JREV == OW_TEST_VF_JREV && VF_JDIFF == OW_TEST_VF_JDIFF && VF_NDECAY == OW_TEST_VF_NDECAY && VF_VSR == OW_TEST_VF_VSR &&
+              VF_COUNT == OW_TEST_VF_COUNT, "openwurli_hip_test.h names the voice record's fields by index");
+int ow_test_engine_read_voice_record(ow_engine* e, int slot, int steal, double* out) {
+    if (!e || !e->pool || !out || slot < 0 || slot >= OW_MAX_VOICES) return -1;
+    ow_pool* p = e->pool;
+    if (hipSetDevice(p->device) != hipSuccess || hipStreamSynchronize(p->stream) != hipSuccess) return -1;
+    const double* src = p->d_vrec + ((size_t)e->index * 2 + (steal ? 1 : 0)) * OW_VREC_DOUBLES + slot;
+    return hipMemcpy2D(out, sizeof(double), src, sizeof(double) * 64, sizeof(double), (size_t)VF_COUNT, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+// The write is a state change behind the scheduler's back, like ow_test_engine_write_chain_rows: a block rendered ahead is forgotten, the
+// voice lists are packed again, and the engine's transient flag -- which of the voice kernels its slot voices get -- is what its sounding
+// slot voices' records now say (VoiceRegs::in_transient: damper bit, sample < onset_n, noise remaining).  Which slots are occupied,
+// releasing or stolen is the host's state machine and comes from the API calls alone.
+int ow_test_engine_write_voice_record(ow_engine* e, int slot, int steal, const double* in) {
+    if (!e || !e->pool || !in || slot < 0 || slot >= OW_MAX_VOICES) return -1;
+    ow_pool* p = e->pool;
+    if (hipSetDevice(p->device) != hipSuccess) return -1;
+    invalidate_spec(p);
+    if (hipStreamSynchronize(p->stream) != hipSuccess) return -1;
+    vm_wait_download(p);                                  // the masks below are the host's copy
+    double* rec0 = p->d_vrec + (size_t)e->index * 2 * OW_VREC_DOUBLES;
+    if (hipMemcpy2D(rec0 + (steal ? OW_VREC_DOUBLES : 0) + slot, sizeof(double) * 64, in, sizeof(double), sizeof(double), (size_t)VF_COUNT,
+                    hipMemcpyHostToDevice) != hipSuccess) return -1;
+    std::vector<double> f(4 * 64);                        // VF_SAMPLE, VF_ONSET_N, VF_RNG, VF_NCNT of every slot voice ...
+    double fl[64];                                        // ... and VF_FLAGS
+    if (hipMemcpy(f.data(), rec0 + (size_t)VF_SAMPLE * 64, sizeof(double) * 4 * 64, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(fl, rec0 + (size_t)VF_FLAGS * 64, sizeof fl, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    static_assert(VF_ONSET_N == VF_SAMPLE + 1 && VF_NCNT == VF_SAMPLE + 3, "the four counters are read in one copy");
+    auto bits = [](double d) { uint64_t u; std::memcpy(&u, &d, 8); return u; };
+    uint8_t tr = 0;
+    for (uint64_t m = e->vm->main_mask; m; m &= m - 1) {
+        const int s = __builtin_ctzll(m);
+        if ((bits(fl[s]) & 1ull) || bits(f[s]) < bits(f[64 + s]) || (uint32_t)bits(f[3 * 64 + s]) > 0u) tr = 1;
+    }
+    p->transient[e->index] = tr;
+    p->lists_valid = false;
+    if (p->d_prev_tr) p->attn_resync = true;              // p->transient moved without the device's copy
+    return 0;
+}
 // plain device-to-host copy (tests read blocks that a render left in HBM: ow_pool_device_output)
 int ow_test_device_read(void* dst_host, const void* src_device, size_t bytes, int device) {
     if (!dst_host || !src_device) return -1;

@@ -390,6 +390,32 @@ __global__ __launch_bounds__(64) OW_VOICE_GENERAL_ATTR void k_voice(const OwCons
 __device__ __noinline__ __attribute__((const)) double env_after(double env0, double d, uint32_t k) {
     return env0 * pow(d, (double)k);
 }
+// The damper variants carry ae = amplitude x envelope, so a mode WITHOUT amplitude carries nothing and its envelope cannot be had back as
+// ae / amplitude: it is stepped on its own when the block ends, from the record as the block found it (damper count, flags, envelope still
+// unwritten), in the reference's order -- damper factor, then decay (reed.rs:228-247, 290).  Such a mode adds nothing to any sum and is
+// quiet in every silence test; what this keeps right is the record.  Rare (a note struck at velocity 0) and out of line.
+// (tests/test_gpu_voice_block.py, released_no_amplitude_* / steal_no_amplitude_*: the closed form env0 * d^L that stood here left the
+// damper's factors out.)
+__device__ __noinline__ double env_damped_after(const double* __restrict__ rec, int m, int L) {
+    double env = rec[(VF_ENV + m) * 64];
+    const uint32_t fl = (uint32_t)dbits(rec[VF_FLAGS * 64]);
+    const bool damp = (fl & 1u) != 0u;
+    bool done = (fl & 2u) != 0u;
+    double t = rec[VF_DCOUNT * 64];
+    const double ramp = rec[VF_DRAMP * 64], rate = rec[(VF_DRATE + m) * 64], mult = rec[(VF_DMULT + m) * 64], d = rec[(VF_DECAY + m) * 64];
+    for (int k = 0; k < L; ++k) {
+        if (damp) {
+            t += 1.0;
+            if (!done) {
+                if (t > ramp) done = true;
+                else env *= exp_neg_small(rate * damper_ramp_pos(t, ramp));
+            }
+            if (done) env *= mult;
+        }
+        env *= d;
+    }
+    return env;
+}
 // FOLD (the steady kernel proper, round 5): the envelope is not a recurrence of its own but the RADIUS of the quadrature pair -- the
 // rotation coefficients carry decay_mult (folded in where they are formed, every 16th sample), `ae` holds the constant amplitude, and
 // the seven `ae *= decay` of every sample are gone (78 -> 72 vector instructions per voice-sample).  (s, c) enter the block multiplied
@@ -854,7 +880,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #pragma unroll
         for (int i = 0; i < 7; ++i) {
             // envelope = ae / amplitude (amplitude read again here rather than held in 14 registers across the block); a mode without
-            // amplitude contributes nothing whatever its envelope is: it keeps decaying by the closed form
+            // amplitude contributes nothing whatever its envelope is: the folded kernel's closed form serves it, the damper variants step it (env_damped_after)
             const double amp = rec[(VF_AMP + i) * 64];
             if (FOLD) {
                 // back to the record's form: envelope env0 * d^L, (s, c) divided by it.  An envelope that has left the normal range (a
@@ -871,7 +897,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                 rec[(VF_S + i) * 64] = so; rec[(VF_C + i) * 64] = co; rec[(VF_ENV + i) * 64] = env; rec[(VF_DRIFT + i) * 64] = v.drift[i];
                 all_quiet = all_quiet && (fabs(amp * env) <= 1e-4);
             } else {
-            const double env = amp != 0.0 ? v.ae[i] / amp : rec[(VF_ENV + i) * 64] * pow(v.decay[i], (double)L);
+            // (a steal wavefront whose crossfades have all run out stops stepping at that chunk, so ae and dt stand there while a mode
+            // without amplitude is stepped over all L: the record of a voice that is dropped after this block, which nobody reads)
+            const double env = amp != 0.0 ? v.ae[i] / amp : env_damped_after(rec, i, L);
             rec[(VF_S + i) * 64] = v.s[i]; rec[(VF_C + i) * 64] = v.c[i]; rec[(VF_ENV + i) * 64] = env; rec[(VF_DRIFT + i) * 64] = v.drift[i];
             fin = fin && isfinite(v.s[i]) && isfinite(v.c[i]) && isfinite(v.ae[i]);
             all_quiet = all_quiet && (fabs(v.ae[i]) <= 1e-4);

@@ -106,6 +106,23 @@ class _EngineHandle:
         if self._lib.ow_test_engine_write_chain_rows(self._h, int(first_row), int(a.size), a.ctypes.data) != 0:
             raise RuntimeError("ow_test_engine_write_chain_rows failed")
 
+    def read_voice_record(self, slot, steal=False):
+        """Test hook (openwurli_hip_test.h): the voice record of `slot` (its steal voice with steal=True) as the last render left it,
+        float64 [VF_COUNT], field-major (u64 fields as their bits)."""
+        out = np.zeros(binding.VOICE_RECORD_FIELDS, dtype=np.float64)
+        if self._lib.ow_test_engine_read_voice_record(self._h, int(slot), 1 if steal else 0, out.ctypes.data) != 0:
+            raise RuntimeError("ow_test_engine_read_voice_record failed")
+        return out
+
+    def write_voice_record(self, slot, record, steal=False):
+        """Test hook (openwurli_hip_test.h): overwrite that voice record before the next block; the engine's transient flag follows the
+        records of its sounding slot voices."""
+        a = np.ascontiguousarray(record, dtype=np.float64)
+        if a.shape != (binding.VOICE_RECORD_FIELDS,):
+            raise ValueError("a voice record is %d doubles" % binding.VOICE_RECORD_FIELDS)
+        if self._lib.ow_test_engine_write_voice_record(self._h, int(slot), 1 if steal else 0, a.ctypes.data) != 0:
+            raise RuntimeError("ow_test_engine_write_voice_record failed")
+
     def reset(self):
         self._lib.ow_engine_reset(self._h)
         binding.raise_if_error(self._lib)

@@ -53,6 +53,111 @@ int owo_engine_poke_voice(void* e, int slot, int steal, int field, double value)
     else return -1;
     return 0;
 }
+// ---- a voice as the product's voice record (tests/voice_block_cases.py) ----
+// Field indices = VF_* of openwurli_amd/csrc/ow_types.h (include/openwurli_hip_test.h names them, guarded by static_asserts there); u64
+// fields travel as their bits.  Only moves: every field of the record is a field of Voice, and the reverse.
+enum { VR_S = 0, VR_C = 7, VR_ENV = 14, VR_DRIFT = 21, VR_COS_INC = 28, VR_SIN_INC = 35, VR_PHASE_INC = 42, VR_AMP = 49, VR_DECAY = 56, VR_DRATE = 63,
+       VR_DMULT = 70, VR_ONSET_INC = 77, VR_ONSET_EXP = 78, VR_DRAMP = 79, VR_DCOUNT = 80, VR_Q = 81, VR_DS = 82, VR_GAIN = 83, VR_NAMP = 84,
+       VR_NB0 = 85, VR_NS1 = 90, VR_NS2 = 91, VR_SAMPLE = 92, VR_ONSET_N = 93, VR_RNG = 94, VR_NCNT = 95, VR_FLAGS = 96, VR_STEAL = 97, VR_BETA = 98,
+       VR_JREV = 99, VR_JDIFF = 100, VR_NDECAY = 101, VR_VSR = 102, VR_COUNT = 103 };
+static double vr_bits(uint64_t u) { double d; std::memcpy(&d, &u, 8); return d; }
+static uint64_t vr_u64(double d) { uint64_t u; std::memcpy(&u, &d, 8); return u; }
+static void vr_store(const Voice& v, uint32_t steal_fade, uint32_t steal_fade_len, double* r) {
+    for (int m = 0; m < NUM_MODES; ++m) {
+        const Mode& md = v.reed.modes[m];
+        r[VR_S + m] = md.s; r[VR_C + m] = md.c; r[VR_ENV + m] = md.envelope; r[VR_DRIFT + m] = md.jitter_drift;
+        r[VR_COS_INC + m] = md.cos_inc; r[VR_SIN_INC + m] = md.sin_inc; r[VR_PHASE_INC + m] = md.phase_inc; r[VR_AMP + m] = md.amplitude;
+        r[VR_DECAY + m] = md.decay_mult; r[VR_DRATE + m] = md.damper_rate; r[VR_DMULT + m] = md.damper_mult;
+    }
+    r[VR_ONSET_INC] = v.reed.onset_ramp_inc; r[VR_ONSET_EXP] = v.reed.onset_shape_exp;
+    r[VR_DRAMP] = v.reed.damper_ramp_samples; r[VR_DCOUNT] = v.reed.damper_release_count;
+    r[VR_Q] = v.pickup.q; r[VR_DS] = v.pickup.displacement_scale; r[VR_GAIN] = v.post_pickup_gain;
+    r[VR_NAMP] = v.noise.amplitude;
+    r[VR_NB0] = v.noise.bpf.b0; r[VR_NB0 + 1] = v.noise.bpf.b1; r[VR_NB0 + 2] = v.noise.bpf.b2; r[VR_NB0 + 3] = v.noise.bpf.a1; r[VR_NB0 + 4] = v.noise.bpf.a2;
+    r[VR_NS1] = v.noise.bpf.s1; r[VR_NS2] = v.noise.bpf.s2;
+    r[VR_SAMPLE] = vr_bits(v.reed.sample); r[VR_ONSET_N] = vr_bits(v.reed.onset_ramp_samples);
+    r[VR_RNG] = vr_bits((uint64_t)v.reed.jitter_state | ((uint64_t)v.noise.rng_state << 32));
+    r[VR_NCNT] = vr_bits((uint64_t)v.noise.remaining | ((uint64_t)v.noise.fade_in_remaining << 32));
+    r[VR_FLAGS] = vr_bits((uint64_t)((v.reed.damper_active ? 1u : 0u) | (v.reed.damper_ramp_done ? 2u : 0u)) | ((uint64_t)(uint32_t)v.midi_note << 32));
+    r[VR_STEAL] = vr_bits((uint64_t)steal_fade | ((uint64_t)steal_fade_len << 32));
+    r[VR_BETA] = v.pickup.beta; r[VR_JREV] = v.reed.jitter_revert; r[VR_JDIFF] = v.reed.jitter_diffusion;
+    r[VR_NDECAY] = v.noise.decay_per_sample; r[VR_VSR] = v.sample_rate;
+}
+static void vr_load(Voice& v, uint32_t& steal_fade, uint32_t& steal_fade_len, const double* r) {
+    for (int m = 0; m < NUM_MODES; ++m) {
+        Mode& md = v.reed.modes[m];
+        md.s = r[VR_S + m]; md.c = r[VR_C + m]; md.envelope = r[VR_ENV + m]; md.jitter_drift = r[VR_DRIFT + m];
+        md.cos_inc = r[VR_COS_INC + m]; md.sin_inc = r[VR_SIN_INC + m]; md.phase_inc = r[VR_PHASE_INC + m]; md.amplitude = r[VR_AMP + m];
+        md.decay_mult = r[VR_DECAY + m]; md.damper_rate = r[VR_DRATE + m]; md.damper_mult = r[VR_DMULT + m];
+    }
+    v.reed.onset_ramp_inc = r[VR_ONSET_INC]; v.reed.onset_shape_exp = r[VR_ONSET_EXP];
+    v.reed.damper_ramp_samples = r[VR_DRAMP]; v.reed.damper_release_count = r[VR_DCOUNT];
+    v.pickup.q = r[VR_Q]; v.pickup.displacement_scale = r[VR_DS]; v.post_pickup_gain = r[VR_GAIN];
+    v.noise.amplitude = r[VR_NAMP];
+    v.noise.bpf.b0 = r[VR_NB0]; v.noise.bpf.b1 = r[VR_NB0 + 1]; v.noise.bpf.b2 = r[VR_NB0 + 2]; v.noise.bpf.a1 = r[VR_NB0 + 3]; v.noise.bpf.a2 = r[VR_NB0 + 4];
+    v.noise.bpf.s1 = r[VR_NS1]; v.noise.bpf.s2 = r[VR_NS2];
+    v.reed.sample = vr_u64(r[VR_SAMPLE]); v.reed.onset_ramp_samples = vr_u64(r[VR_ONSET_N]);
+    v.reed.jitter_state = (uint32_t)vr_u64(r[VR_RNG]); v.noise.rng_state = (uint32_t)(vr_u64(r[VR_RNG]) >> 32);
+    v.noise.remaining = (uint32_t)vr_u64(r[VR_NCNT]); v.noise.fade_in_remaining = (uint32_t)(vr_u64(r[VR_NCNT]) >> 32);
+    const uint64_t fl = vr_u64(r[VR_FLAGS]);
+    v.reed.damper_active = (fl & 1u) != 0; v.reed.damper_ramp_done = (fl & 2u) != 0; v.midi_note = (int)(uint32_t)(fl >> 32);
+    steal_fade = (uint32_t)vr_u64(r[VR_STEAL]); steal_fade_len = (uint32_t)(vr_u64(r[VR_STEAL]) >> 32);
+    v.pickup.beta = r[VR_BETA]; v.reed.jitter_revert = r[VR_JREV]; v.reed.jitter_diffusion = r[VR_JDIFF];
+    v.noise.decay_per_sample = r[VR_NDECAY]; v.sample_rate = r[VR_VSR];
+}
+// The voice of `slot` (steal != 0: its steal voice) with the slot's steal counters, out of / into the engine.  Return 0, -1 if the slot
+// has no such voice (set: the voice must exist -- which slots sound is the engine's own state).
+int owo_engine_voice_record(void* e, int slot, int steal, double* record) {
+    WurliEngine* w = (WurliEngine*)e;
+    if (slot < 0 || slot >= MAX_VOICES) return -1;
+    const VoiceSlot& s = w->voices[slot];
+    const Voice* v = steal ? s.steal_voice.get() : s.voice.get();
+    if (!v) return -1;
+    vr_store(*v, s.steal_fade, s.steal_fade_len, record);
+    return 0;
+}
+int owo_engine_set_voice_record(void* e, int slot, int steal, const double* record) {
+    WurliEngine* w = (WurliEngine*)e;
+    if (slot < 0 || slot >= MAX_VOICES) return -1;
+    VoiceSlot& s = w->voices[slot];
+    Voice* v = steal ? s.steal_voice.get() : s.voice.get();
+    if (!v) return -1;
+    uint32_t fade, len;
+    vr_load(*v, fade, len, record);
+    if (steal) { s.steal_fade = fade; s.steal_fade_len = len; }
+    return 0;
+}
+// One block of one voice as a function of its record: a Voice built from record_in, the unchanged Voice::render over L samples, for a steal
+// voice the crossfade and the counter of engine.rs:483-490, the record written back.  y_out [L]: what the voice adds to the engine's sum.
+// info [3]: Voice::is_silent() after the block; still inside an onset ramp, a noise burst or a damper phase (what keeps an engine with
+// the general voice kernels); every sample and the state finite.  Returns 0, <0 on a bad argument.
+int owo_voice_block(const double* record_in, int steal, size_t L, double* record_out, double* y_out, int* info) {
+    if (!record_in || !record_out || !y_out || !info || L == 0) return -1;
+    Voice v;
+    uint32_t fade, len;
+    vr_load(v, fade, len, record_in);
+    v.render(y_out, L);
+    bool finite = true;
+    for (size_t i = 0; i < L; ++i) finite = finite && std::isfinite(y_out[i]);
+    if (steal) {
+        const double fade_len = (double)len;
+        for (size_t i = 0; i < L; ++i) {
+            const uint32_t ii = (uint32_t)i;
+            const uint32_t remaining = fade > ii ? fade - ii : 0u;
+            const double gain = (double)remaining / fade_len;
+            y_out[i] = y_out[i] * gain;
+        }
+        const uint32_t l32 = (uint32_t)L;
+        fade = fade > l32 ? fade - l32 : 0u;
+    }
+    vr_store(v, fade, len, record_out);
+    finite = finite && std::isfinite(v.pickup.q);
+    for (int m = 0; m < NUM_MODES; ++m) finite = finite && std::isfinite(v.reed.modes[m].s) && std::isfinite(v.reed.modes[m].c) && std::isfinite(v.reed.modes[m].envelope);
+    info[0] = v.is_silent() ? 1 : 0;
+    info[1] = (v.reed.damper_active || v.reed.sample < v.reed.onset_ramp_samples || !v.noise.is_done()) ? 1 : 0;
+    info[2] = finite ? 1 : 0;
+    return 0;
+}
 // n steps of the tremolo cell alone (Tremolo::process: oscillator + LED + CdS envelope), results discarded: what the product's
 // ow_test_pool_stagger_tremolo does to a phase group, so that staggered engines can be compared with the oracle
 void owo_engine_advance_tremolo(void* e, size_t n) {

@@ -443,3 +443,171 @@ def _render_note(midi, v, dur, sr, T, taps):
                           "decay_db": [float(d) for d in decay_db], "ds": float(ds), "gain": float(gain), "onset_samples": ramp_samps,
                           "onset_exp": float(shape)}
     return out
+
+
+# ------------------------------------------------------------------------------------------------ one block from a voice record
+# The same statements as _render_note's sample loop, started from a voice record instead of Voice::note_on, with what render_note never
+# reaches: the damper (reed.rs:226-247), Voice::is_silent (voice.rs:183-188, reed.rs:309-314) and a steal voice's crossfade
+# (engine.rs:483-490).  The record is the product's (VF_* of openwurli_amd/csrc/ow_types.h: every field is a field of Voice); u64 fields
+# travel as the bits of a double.  tests/test_oracle_voice_block_cases.py holds it to the C++ oracle's owo_voice_block.
+VF = dict(S=0, C=7, ENV=14, DRIFT=21, COS_INC=28, SIN_INC=35, PHASE_INC=42, AMP=49, DECAY=56, DRATE=63, DMULT=70, ONSET_INC=77, ONSET_EXP=78,
+          DRAMP=79, DCOUNT=80, Q=81, DS=82, GAIN=83, NAMP=84, NB0=85, NS1=90, NS2=91, SAMPLE=92, ONSET_N=93, RNG=94, NCNT=95, FLAGS=96,
+          STEAL=97, BETA=98, JREV=99, JDIFF=100, NDECAY=101, VSR=102, COUNT=103)
+# deliberate slips, one per name: what tests/test_oracle_voice_block_cases.py requires the comparison to see
+MUTANTS = ("renorm_late", "jitter_on_1", "env_write_back", "onset_index", "crossfade_remaining", "damper_final_mult", "fade_table", "knee_095")
+U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def rec_u64(record, field):
+    return int(np.asarray(record, dtype=np.float64)[field:field + 1].view(np.uint64)[0])
+
+
+def u64_bits(x):
+    return float(np.array([int(x) & U64], dtype=np.uint64).view(np.float64)[0])
+
+
+def voice_block(record, steal, L, T=np.float64, mutant=None):
+    """One block of L samples of the voice in `record` (float64 [103]).  Returns (record_out float64 [103], y float64 [L], info) with
+    info = dict(silent, transient, finite, ramp_done, sat int8 [L]: the saturated side of the pickup input per sample (-1, 0, +1),
+    x float64 [L]: the pickup's input before the displacement scale)."""
+    assert mutant is None or mutant in MUTANTS, mutant
+    old = np.seterr(all="ignore")
+    try:
+        return _voice_block(np.asarray(record, dtype=np.float64), bool(steal), int(L), T, mutant)
+    finally:
+        np.seterr(**old)
+
+
+def _voice_block(r, steal, L, T, mutant):
+    f = F(T)
+    M = range(NUM_MODES)
+    col = lambda k: [T(r[VF[k] + m]) for m in M]
+    s, c, env, drift = col("S"), col("C"), col("ENV"), col("DRIFT")
+    cos_inc, sin_inc, phase_inc, amps, decay_mult = col("COS_INC"), col("SIN_INC"), col("PHASE_INC"), col("AMP"), col("DECAY")
+    drate, dmult = col("DRATE"), col("DMULT")
+    ramp_inc, shape = T(r[VF["ONSET_INC"]]), T(r[VF["ONSET_EXP"]])
+    dramp, dcount = T(r[VF["DRAMP"]]), T(r[VF["DCOUNT"]])
+    q, ds, gain = T(r[VF["Q"]]), T(r[VF["DS"]]), T(r[VF["GAIN"]])
+    namp = T(r[VF["NAMP"]])
+    b0, b1, b2, a1, a2 = [T(r[VF["NB0"] + i]) for i in range(5)]
+    z1, z2 = T(r[VF["NS1"]]), T(r[VF["NS2"]])
+    sample, ramp_samps = rec_u64(r, VF["SAMPLE"]), rec_u64(r, VF["ONSET_N"])
+    js, nrng = rec_u64(r, VF["RNG"]) & U32, rec_u64(r, VF["RNG"]) >> 32
+    nrem, nfade = rec_u64(r, VF["NCNT"]) & U32, rec_u64(r, VF["NCNT"]) >> 32
+    flags = rec_u64(r, VF["FLAGS"])
+    damper_active, ramp_done, midi = bool(flags & 1), bool(flags & 2), flags >> 32
+    fade, fade_len = rec_u64(r, VF["STEAL"]) & U32, rec_u64(r, VF["STEAL"]) >> 32
+    beta, revert, diffusion, ndecay, sr = T(r[VF["BETA"]]), T(r[VF["JREV"]]), T(r[VF["JDIFF"]]), T(r[VF["NDECAY"]]), T(r[VF["VSR"]])
+    half = T(4294967295.0) / T(2.0)
+    pi = T(3.14159265358979323846264338327950288)
+    knee = T(0.95) if mutant == "knee_095" else T(0.94)
+    y_out = np.zeros(L, dtype=np.float64)
+    sat = np.zeros(L, dtype=np.int8)
+    xs = np.zeros(L, dtype=np.float64)
+    finite = True
+    for k in range(L):
+        # ModalReed::render, one sample (reed.rs:223-305)
+        if damper_active:                                                        # reed.rs:226-247
+            dcount = dcount + T(1.0)
+            t = dcount
+            ended_now = False
+            if not ramp_done:
+                if t > dramp:
+                    ramp_done = True
+                    ended_now = True
+                else:
+                    for m in M:
+                        inst_rate = drate[m] * t / dramp
+                        env[m] = env[m] * f.exp(-inst_rate)
+            if ramp_done and not (mutant == "damper_final_mult" and ended_now):
+                for m in M:
+                    env[m] = env[m] * dmult[m]
+        if sample < ramp_samps:                                                  # reed.rs:251-264
+            nn = sample + 1 if mutant == "onset_index" else sample
+            cosine = T(0.5) * (T(1.0) - f.cos(T(nn) * ramp_inc))
+            if shape <= 1.001:
+                onset = cosine
+            elif shape >= 1.999:
+                onset = cosine * cosine
+            else:
+                onset = f.pow(cosine, shape)
+        else:
+            onset = T(1.0)
+        if sample & 15 == (1 if mutant == "jitter_on_1" else 0):                 # reed.rs:267-272
+            for m in M:
+                js = lcg(js)
+                u = T(js >> 1) / half
+                noise = (u * T(2.0) - T(1.0)) * T(1.7320508080)
+                drift[m] = revert * drift[m] + diffusion * noise
+        acc = T(0.0)
+        for m in M:                                                              # reed.rs:275-291
+            acc = acc + amps[m] * s[m] * onset * env[m]
+            dp = drift[m] * phase_inc[m]
+            ci = cos_inc[m] - dp * sin_inc[m]
+            si = sin_inc[m] + dp * cos_inc[m]
+            s_new = s[m] * ci + c[m] * si
+            c_new = c[m] * ci - s[m] * si
+            s[m], c[m] = s_new, c_new
+            if not (mutant == "env_write_back" and k == L - 1):
+                env[m] = env[m] * decay_mult[m]
+        at = sample - 1 if mutant == "renorm_late" else sample
+        if at & 1023 == 0 and at > 0:                                            # reed.rs:294-301
+            for m in M:
+                r_inv = T(1.0) / f.sqrt(s[m] * s[m] + c[m] * c[m])
+                s[m] = s[m] * r_inv
+                c[m] = c[m] * r_inv
+        x = T(0.0) + acc
+        sample = (sample + 1) & U64
+        if nrem > 0:                                                             # AttackNoise::render (hammer.rs:150-179)
+            if nfade > 0:
+                pos = 16 - nfade + (1 if mutant == "fade_table" else 0)
+                t = T(pos) / T(16.0)
+                nfade -= 1
+                e = T(0.5) * (T(1.0) - f.cos(pi * t))
+            else:
+                e = T(1.0)
+            nrng = lcg(nrng)
+            signed = nrng - (1 << 32) if nrng & 0x80000000 else nrng
+            nz = T(signed) / T(2147483647.0)
+            yb = b0 * nz + z1
+            z1 = b1 * nz - a1 * yb + z2
+            z2 = b2 * nz - a2 * yb
+            x = x + namp * e * yb
+            namp = namp * ndecay
+            nrem -= 1
+        xs[k] = np.float64(x)
+        y = x * ds                                                               # Pickup::process (pickup.rs:130-149, 72-80)
+        ay = abs(y)
+        if not (ay < knee):
+            rng_ = T(0.98) - knee
+            y = np.copysign(knee + rng_ * f.tanh((ay - knee) / rng_), y)
+            sat[k] = 1 if y > 0 else -1
+        omy = T(1.0) - y
+        al = beta * omy
+        q = (q * (T(1.0) - al) + T(2.0) * beta) / (T(1.0) + al)
+        o = ((q * omy - T(1.0)) * T(1.8375)) * gain                              # voice.rs:174-178
+        finite = finite and bool(np.isfinite(o))
+        if steal:                                                                # engine.rs:483-489
+            remaining = fade - k if fade > k else 0
+            if mutant == "crossfade_remaining":
+                remaining = max(remaining - 1, 0)
+            o = o * (T(remaining) / T(fade_len))
+        y_out[k] = np.float64(o)
+    if steal:
+        fade = fade - L if fade > L else 0                                       # engine.rs:490
+    out = r.copy()
+    for m in M:
+        out[VF["S"] + m], out[VF["C"] + m], out[VF["ENV"] + m], out[VF["DRIFT"] + m] = s[m], c[m], env[m], drift[m]
+    out[VF["DCOUNT"]], out[VF["Q"]], out[VF["NAMP"]], out[VF["NS1"]], out[VF["NS2"]] = dcount, q, namp, z1, z2
+    out[VF["SAMPLE"]] = u64_bits(sample)
+    out[VF["RNG"]] = u64_bits(js | (nrng << 32))
+    out[VF["NCNT"]] = u64_bits(nrem | (nfade << 32))
+    out[VF["FLAGS"]] = u64_bits((1 if damper_active else 0) | (2 if ramp_done else 0) | (midi << 32))
+    out[VF["STEAL"]] = u64_bits(fade | (fade_len << 32))
+    finite = finite and all(bool(np.isfinite(v)) for v in [q] + s + c + env)
+    thr = f.pow(T(10.0), T(-80.0) / T(20.0))                                     # reed.rs:309-314
+    silent = all(abs(amps[m] * env[m]) <= thr for m in M)
+    if damper_active and dcount / sr > 10.0:                                     # voice.rs:183-188
+        silent = True
+    return out, y_out, dict(silent=bool(silent), transient=bool(damper_active or sample < ramp_samps or nrem > 0), finite=finite,
+                            ramp_done=bool(ramp_done), sat=sat, x=xs)

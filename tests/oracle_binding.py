@@ -137,6 +137,17 @@ class OracleEngine:
         assert rows.shape == (STAGE_ROW_COUNT,)
         self.L.owo_engine_set_stage_rows(self.h, _p(rows))
 
+    def voice_record(self, slot, steal=False):
+        """the voice of `slot` (its steal voice) with the slot's steal counters as the product's voice record (float64 [VOICE_RECORD_FIELDS],
+        VF_* indices, u64 fields as their bits); None if the slot has no such voice"""
+        rec = np.zeros(VOICE_RECORD_FIELDS)
+        return rec if self.L.owo_engine_voice_record(self.h, int(slot), 1 if steal else 0, _p(rec)) == 0 else None
+
+    def set_voice_record(self, slot, record, steal=False):
+        record = np.ascontiguousarray(record, dtype=np.float64)
+        assert record.shape == (VOICE_RECORD_FIELDS,)
+        assert self.L.owo_engine_set_voice_record(self.h, int(slot), 1 if steal else 0, _p(record)) == 0, (slot, steal)
+
     def count_voices_in_state(self, st): return self.L.owo_engine_count_state(self.h, int(st))
     def active_voice_count(self): return self.L.owo_engine_active_voice_count(self.h)
     def steal_voice_count(self): return self.L.owo_engine_steal_voice_count(self.h)
@@ -187,6 +198,20 @@ def output_stage_block(host_rate, rows_in, tap, n, set_flags=0, spk_target=0.0, 
     assert rc == 0, rc
     m = n * osr
     return rows_out, out, dict(sweeps=info[:m], converged=info[m:2 * m], redesigned=info[2 * m:2 * m + n], fired=info[2 * m + n:], out64=out64)
+
+
+VOICE_RECORD_FIELDS = 103        # VF_COUNT of openwurli_amd/csrc/ow_types.h
+
+
+def voice_block(record, steal, length):
+    """One block of `length` samples of one voice from its record (owo_voice_block: Voice::render, and for a steal voice the crossfade of
+    engine.rs:483-490).  Returns (record_out, y float64 [length], dict(silent, transient, finite))."""
+    record = np.ascontiguousarray(record, dtype=np.float64)
+    assert record.shape == (VOICE_RECORD_FIELDS,)
+    out = np.zeros(VOICE_RECORD_FIELDS); y = np.zeros(int(length)); info = np.zeros(3, dtype=np.int32)
+    rc = lib().owo_voice_block(_p(record), 1 if steal else 0, int(length), _p(out), _p(y), _p(info))
+    assert rc == 0, rc
+    return out, y, dict(silent=bool(info[0]), transient=bool(info[1]), finite=bool(info[2]))
 
 
 def dk_step_cases(rate, states, inputs, g_ldr, g_ldr_prev, perturbed=False):
