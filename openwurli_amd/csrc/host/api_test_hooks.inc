@@ -459,154 +459,143 @@ int ow_test_pool_trajectory_state(const ow_pool* p, uint64_t out[5]) {
 }
 
 // ---- diagnostics ---------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// One diagnostic run: the host arrays `in` copied into device buffers of their own (a null array: the buffer alone), the outputs `out`
+// zeroed on the device, launch(inputs, outputs), the launch checked, the outputs copied back (a null array: workspace, left behind).
+struct DebugIn { const void* host; size_t bytes; };
+struct DebugOut { void* host; size_t bytes; };
+template <class Launch> void debug_run(std::initializer_list<DebugIn> in, std::initializer_list<DebugOut> out, Launch launch) {
+    std::vector<DevMem> di(in.size()), dout(out.size());
+    size_t k = 0;
+    for (const DebugIn& a : in) { di[k].alloc(a.bytes); if (a.host) HIP_OK(hipMemcpy(di[k].p, a.host, a.bytes, hipMemcpyHostToDevice)); ++k; }
+    k = 0;
+    for (const DebugOut& a : out) { dout[k].alloc(a.bytes); HIP_OK(hipMemset(dout[k].p, 0, a.bytes)); ++k; }
+    launch(di.data(), dout.data());
+    HIP_OK(hipGetLastError());
+    k = 0;
+    for (const DebugOut& a : out) { if (a.host) HIP_OK(hipMemcpy(a.host, dout[k].p, a.bytes, hipMemcpyDeviceToHost)); ++k; }
+}
+// A diagnostics hook's body under the hook's name: 0, or -1 with "<name>: <what went wrong>" as the library's last error.
+template <class Body> int debug_hook(const char* name, Body body) {
+    try { body(); return 0; } catch (const std::exception& ex) { (void)hipGetLastError(); set_err(std::string(name) + ": " + ex.what()); return -1; }
+}
+// The constants of the chain rate `rate`.  build_consts takes the HOST rate; a host rate >= 88.2 kHz runs the chain at that rate without
+// oversampling (engine.rs:195)
+std::unique_ptr<OwConsts> chain_rate_consts(double rate, int preamp_kind) {
+    std::unique_ptr<OwConsts> hc(new OwConsts());
+    owhip::build_consts(*hc, rate < 88200.0 ? rate * 0.5 : rate, preamp_kind);
+    if (hc->os_sr != rate) throw std::runtime_error("rate is not reachable as a chain rate");
+    return hc;
+}
+}  // namespace
+extern "C" {
 int ow_debug_mlp_raw(const uint8_t* notes, const double* velocities, size_t n, double* out, int use_mfma, int device) {
-    try {
+    return debug_hook("ow_debug_mlp_raw", [&] {
         if (!notes || !velocities || !out || n == 0) throw std::runtime_error("null argument");
         HIP_OK(hipSetDevice(device));
-        DevMem dn, dv, dout;
-        dn.alloc(n); dv.alloc(n * sizeof(double)); dout.alloc(n * 11 * sizeof(double));
-        HIP_OK(hipMemcpy(dn.p, notes, n, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(dv.p, velocities, n * sizeof(double), hipMemcpyHostToDevice));
-        owdev::k_debug_mlp<<<dim3((unsigned)((n + 63) / 64)), dim3(64)>>>(dn.as<uint8_t>(), dv.as<double>(), (int)n, dout.as<double>(), use_mfma);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpy(out, dout.p, n * 11 * sizeof(double), hipMemcpyDeviceToHost));
-        return 0;
-    } catch (const std::exception& ex) { set_err(std::string("ow_debug_mlp_raw: ") + ex.what()); return -1; }
+        debug_run({{notes, n}, {velocities, n * sizeof(double)}}, {{out, n * 11 * sizeof(double)}}, [&](const DevMem* i, const DevMem* o) {
+            owdev::k_debug_mlp<<<dim3((unsigned)((n + 63) / 64)), dim3(64)>>>(i[0].as<uint8_t>(), i[1].as<double>(), (int)n, o[0].as<double>(), use_mfma);
+        });
+    });
 }
 
 int ow_debug_div(const double* a, const double* b, size_t n, double* fast, double* ieee, int device) {
-    try {
+    return debug_hook("ow_debug_div", [&] {
         if (!a || !b || !fast || !ieee) throw std::runtime_error("null argument");
-        if (n == 0) return 0;
+        if (n == 0) return;
         HIP_OK(hipSetDevice(device));
-        DevMem da, db, df, di;
-        da.alloc(n * sizeof(double)); db.alloc(n * sizeof(double)); df.alloc(n * sizeof(double)); di.alloc(n * sizeof(double));
-        HIP_OK(hipMemcpy(da.p, a, n * sizeof(double), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(db.p, b, n * sizeof(double), hipMemcpyHostToDevice));
-        owdev::k_debug_div<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(da.as<double>(), db.as<double>(), n, df.as<double>(), di.as<double>());
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpy(fast, df.p, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(ieee, di.p, n * sizeof(double), hipMemcpyDeviceToHost));
-        return 0;
-    } catch (const std::exception& ex) { set_err(std::string("ow_debug_div: ") + ex.what()); return -1; }
+        const size_t d = n * sizeof(double);
+        debug_run({{a, d}, {b, d}}, {{fast, d}, {ieee, d}}, [&](const DevMem* i, const DevMem* o) {
+            owdev::k_debug_div<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(i[0].as<double>(), i[1].as<double>(), n, o[0].as<double>(), o[1].as<double>());
+        });
+    });
 }
 
 int ow_debug_div_const(int which, const double* a, size_t n, double* fast, double* ieee, uint64_t* mismatches, int device) {
-    try {
+    return debug_hook("ow_debug_div_const", [&] {
         if (which < 0 || which > 7) throw std::runtime_error("unknown constant");
         HIP_OK(hipSetDevice(device));
         if (!a) {
             if (!mismatches) throw std::runtime_error("null argument");
             if (which != 0 && which != 6) throw std::runtime_error("no exhaustive numerator set for this constant");
-            DevMem dm;
-            dm.alloc(sizeof(unsigned long long));
-            HIP_OK(hipMemset(dm.p, 0, sizeof(unsigned long long)));
-            owdev::k_debug_div_draw_all<<<dim3(4096), dim3(256)>>>(which, dm.as<unsigned long long>());
-            HIP_OK(hipGetLastError());
             unsigned long long h = 0;
-            HIP_OK(hipMemcpy(&h, dm.p, sizeof h, hipMemcpyDeviceToHost));
+            debug_run({}, {{&h, sizeof h}}, [&](const DevMem*, const DevMem* o) {
+                owdev::k_debug_div_draw_all<<<dim3(4096), dim3(256)>>>(which, o[0].as<unsigned long long>());
+            });
             *mismatches = h;
-            return 0;
+            return;
         }
         if (!fast || !ieee) throw std::runtime_error("null argument");
-        if (n == 0) return 0;
-        DevMem da, df, di;
-        da.alloc(n * sizeof(double)); df.alloc(n * sizeof(double)); di.alloc(n * sizeof(double));
-        HIP_OK(hipMemcpy(da.p, a, n * sizeof(double), hipMemcpyHostToDevice));
-        owdev::k_debug_div_const<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(which, da.as<double>(), n, df.as<double>(), di.as<double>());
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpy(fast, df.p, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(ieee, di.p, n * sizeof(double), hipMemcpyDeviceToHost));
-        return 0;
-    } catch (const std::exception& ex) { set_err(std::string("ow_debug_div_const: ") + ex.what()); return -1; }
+        if (n == 0) return;
+        const size_t d = n * sizeof(double);
+        debug_run({{a, d}}, {{fast, d}, {ieee, d}}, [&](const DevMem* i, const DevMem* o) {
+            owdev::k_debug_div_const<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(which, i[0].as<double>(), n, o[0].as<double>(), o[1].as<double>());
+        });
+    });
 }
 
 int ow_debug_div_forms(int mode, const double* a, const double* b, const double* y, size_t n, double* fast, double* ieee, int device) {
-    try {
+    return debug_hook("ow_debug_div_forms", [&] {
         if (!a || !b || !fast || !ieee || mode < 0 || mode > 2 || (mode == 0 && !y)) throw std::runtime_error("bad argument");
-        if (n == 0) return 0;
+        if (n == 0) return;
         HIP_OK(hipSetDevice(device));
-        DevMem da, db, dy, df, di;
-        da.alloc(n * sizeof(double)); db.alloc(n * sizeof(double)); dy.alloc(n * sizeof(double)); df.alloc(n * sizeof(double)); di.alloc(n * sizeof(double));
-        HIP_OK(hipMemcpy(da.p, a, n * sizeof(double), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(db.p, b, n * sizeof(double), hipMemcpyHostToDevice));
-        if (y) HIP_OK(hipMemcpy(dy.p, y, n * sizeof(double), hipMemcpyHostToDevice));
-        owdev::k_debug_div_forms<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(mode, da.as<double>(), db.as<double>(), dy.as<double>(), n, df.as<double>(), di.as<double>());
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpy(fast, df.p, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(ieee, di.p, n * sizeof(double), hipMemcpyDeviceToHost));
-        return 0;
-    } catch (const std::exception& ex) { set_err(std::string("ow_debug_div_forms: ") + ex.what()); return -1; }
+        const size_t d = n * sizeof(double);
+        debug_run({{a, d}, {b, d}, {y, d}}, {{fast, d}, {ieee, d}}, [&](const DevMem* i, const DevMem* o) {
+            owdev::k_debug_div_forms<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(mode, i[0].as<double>(), i[1].as<double>(), i[2].as<double>(), n, o[0].as<double>(), o[1].as<double>());
+        });
+    });
 }
 
 int ow_debug_unary(int which, const double* x, size_t n, double* fast, double* lib, int device) {
-    try {
+    return debug_hook("ow_debug_unary", [&] {
         if (!x || !fast || !lib || which < 0 || which > 6) throw std::runtime_error("null argument or unknown function");
-        if (n == 0) return 0;
+        if (n == 0) return;
         HIP_OK(hipSetDevice(device));
-        DevMem dx, df, dl;
-        dx.alloc(n * sizeof(double)); df.alloc(n * sizeof(double)); dl.alloc(n * sizeof(double));
-        HIP_OK(hipMemcpy(dx.p, x, n * sizeof(double), hipMemcpyHostToDevice));
-        owdev::k_debug_exp<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(which, dx.as<double>(), n, df.as<double>(), dl.as<double>());
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpy(fast, df.p, n * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(lib, dl.p, n * sizeof(double), hipMemcpyDeviceToHost));
-        return 0;
-    } catch (const std::exception& ex) { set_err(std::string("ow_debug_unary: ") + ex.what()); return -1; }
+        const size_t d = n * sizeof(double);
+        debug_run({{x, d}}, {{fast, d}, {lib, d}}, [&](const DevMem* i, const DevMem* o) {
+            owdev::k_debug_exp<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(which, i[0].as<double>(), n, o[0].as<double>(), o[1].as<double>());
+        });
+    });
 }
 
 int ow_debug_dk_step(int form, double rate, const double* states_in, const double* input, const double* g_ldr, const double* g_ldr_prev, size_t n,
                      double* states_out, double* out, int device) {
-    try {
+    return debug_hook("ow_debug_dk_step", [&] {
         if (!states_in || !input || !g_ldr || !g_ldr_prev || !states_out || !out || form < 0 || form > 3 || !(rate > 0.0)) throw std::runtime_error("bad argument");
-        if (n == 0) return 0;
+        if (n == 0) return;
         if (n > (size_t)1 << 24) throw std::runtime_error("too many cases");
         HIP_OK(hipSetDevice(device));
-        std::unique_ptr<OwConsts> hc(new OwConsts());
-        // build_consts takes the HOST rate; a host rate >= 88.2 kHz runs the chain at that rate without oversampling (engine.rs:195)
-        owhip::build_consts(*hc, rate < 88200.0 ? rate * 0.5 : rate, OW_PREAMP_LEGACY8);
-        if (hc->os_sr != rate) throw std::runtime_error("rate is not reachable as a chain rate");
+        const std::unique_ptr<OwConsts> hc = chain_rate_consts(rate, OW_PREAMP_LEGACY8);
         std::vector<double> rows(14 * n);                      // the chain kernels' state rows: [field][case]
         for (size_t c = 0; c < n; ++c)
             for (int f = 0; f < 14; ++f) rows[(size_t)f * n + c] = states_in[c * 14 + f];
-        DevMem dK, dIn, dX, dG, dGp, dOut, dO;
-        dK.alloc(sizeof(OwConsts)); dIn.alloc(sizeof(double) * 14 * n); dOut.alloc(sizeof(double) * 14 * n);
-        dX.alloc(sizeof(double) * n); dG.alloc(sizeof(double) * n); dGp.alloc(sizeof(double) * n); dO.alloc(sizeof(double) * n);
-        HIP_OK(hipMemcpy(dK.p, hc.get(), sizeof(OwConsts), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(dIn.p, rows.data(), sizeof(double) * 14 * n, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(dX.p, input, sizeof(double) * n, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(dG.p, g_ldr, sizeof(double) * n, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(dGp.p, g_ldr_prev, sizeof(double) * n, hipMemcpyHostToDevice));
-        HIP_OK(hipMemset(dOut.p, 0, sizeof(double) * 14 * n));
-        HIP_OK(hipMemset(dO.p, 0, sizeof(double) * n));
+        const size_t d = sizeof(double) * n;
         const size_t per_wave[4] = {64, 128, 16, 4};            // cases of one wavefront: lane | lane = (main, shadow) | quad | row of sixteen
         const dim3 grid((unsigned)((n + per_wave[form] - 1) / per_wave[form])), block(64);
-        const OwConsts* K = dK.as<OwConsts>();
-        switch (form) {
-            case 0: owdev::k_debug_dk_step<owdev::DKF_LANE><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
-            case 1: owdev::k_debug_dk_step<owdev::DKF_PAIR><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
-            case 2: owdev::k_debug_dk_step<owdev::DKF_WIDE><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
-            default: owdev::k_debug_dk_step<owdev::DKF_ROW><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
-        }
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpy(rows.data(), dOut.p, sizeof(double) * 14 * n, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(out, dO.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+        debug_run({{hc.get(), sizeof(OwConsts)}, {rows.data(), 14 * d}, {input, d}, {g_ldr, d}, {g_ldr_prev, d}}, {{rows.data(), 14 * d}, {out, d}},
+                  [&](const DevMem* i, const DevMem* o) {
+            const OwConsts* K = i[0].as<OwConsts>();
+            const DevMem &dIn = i[1], &dX = i[2], &dG = i[3], &dGp = i[4], &dOut = o[0], &dO = o[1];
+            switch (form) {
+                case 0: owdev::k_debug_dk_step<owdev::DKF_LANE><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
+                case 1: owdev::k_debug_dk_step<owdev::DKF_PAIR><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
+                case 2: owdev::k_debug_dk_step<owdev::DKF_WIDE><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
+                default: owdev::k_debug_dk_step<owdev::DKF_ROW><<<grid, block>>>(K, dIn.as<double>(), dX.as<double>(), dG.as<double>(), dGp.as<double>(), (int)n, dOut.as<double>(), dO.as<double>()); break;
+            }
+        });
         for (size_t c = 0; c < n; ++c)
             for (int f = 0; f < 14; ++f) states_out[c * 14 + f] = rows[(size_t)f * n + c];
-        return 0;
-    } catch (const std::exception& ex) { set_err(std::string("ow_debug_dk_step: ") + ex.what()); return -1; }
+    });
 }
 
 int ow_debug_trem_step(int form, double rate, const double* states_in, size_t n, double* states_out, double* out, unsigned long long* info, int device) {
-    try {
+    return debug_hook("ow_debug_trem_step", [&] {
         if (!states_in || !states_out || !out || !info || form < 0 || form > 2 || !(rate > 0.0)) throw std::runtime_error("bad argument");
-        if (n == 0) return 0;
+        if (n == 0) return;
         if (n > (size_t)1 << 22) throw std::runtime_error("too many cases");
         HIP_OK(hipSetDevice(device));
-        std::unique_ptr<OwConsts> hc(new OwConsts());
-        // build_consts takes the HOST rate; a host rate >= 88.2 kHz runs the chain at that rate without oversampling (engine.rs:195)
-        owhip::build_consts(*hc, rate < 88200.0 ? rate * 0.5 : rate, OW_PREAMP_LEGACY8);
-        if (hc->os_sr != rate) throw std::runtime_error("rate is not reachable as a chain rate");
+        const std::unique_ptr<OwConsts> hc = chain_rate_consts(rate, OW_PREAMP_LEGACY8);
         // the eighteen tremolo rows: [field][case] for the lane and quad forms, [case][field] for the row form; cell at rest, counter 0
         const bool by_case = form == 2;
         auto at = [&](size_t f, size_t c) { return by_case ? c * 18 + f : f * n + c; };
@@ -615,42 +604,30 @@ int ow_debug_trem_step(int form, double rate, const double* states_in, size_t n,
             for (size_t f = 0; f < 15; ++f) rows[at(f, c)] = states_in[c * 15 + f];
             rows[at(CS_T_RLDR, c)] = 1000000.0;
         }
-        DevMem dK, dIn, dOut, dO, dI;
-        dK.alloc(sizeof(OwConsts)); dIn.alloc(sizeof(double) * 18 * n); dOut.alloc(sizeof(double) * 18 * n);
-        dO.alloc(sizeof(double) * n); dI.alloc(sizeof(unsigned long long) * n);
-        HIP_OK(hipMemcpy(dK.p, hc.get(), sizeof(OwConsts), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(dIn.p, rows.data(), sizeof(double) * 18 * n, hipMemcpyHostToDevice));
-        HIP_OK(hipMemset(dOut.p, 0, sizeof(double) * 18 * n));
-        HIP_OK(hipMemset(dO.p, 0, sizeof(double) * n));
-        HIP_OK(hipMemset(dI.p, 0, sizeof(unsigned long long) * n));
         const size_t per_wave[3] = {64, 16, 1};                  // cases of one wavefront: lane | quad | the whole wavefront
         const dim3 grid((unsigned)((n + per_wave[form] - 1) / per_wave[form])), block(64);
-        const OwConsts* K = dK.as<OwConsts>();
-        switch (form) {
-            case 0: owdev::k_debug_trem_step<owdev::TSF_LANE><<<grid, block>>>(K, dIn.as<double>(), (int)n, dOut.as<double>(), dO.as<double>(), dI.as<unsigned long long>()); break;
-            case 1: owdev::k_debug_trem_step<owdev::TSF_WIDE><<<grid, block>>>(K, dIn.as<double>(), (int)n, dOut.as<double>(), dO.as<double>(), dI.as<unsigned long long>()); break;
-            default: owdev::k_debug_trem_step<owdev::TSF_ROW><<<grid, block>>>(K, dIn.as<double>(), (int)n, dOut.as<double>(), dO.as<double>(), dI.as<unsigned long long>()); break;
-        }
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpy(rows.data(), dOut.p, sizeof(double) * 18 * n, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(out, dO.p, sizeof(double) * n, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(info, dI.p, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+        debug_run({{hc.get(), sizeof(OwConsts)}, {rows.data(), sizeof(double) * 18 * n}},
+                  {{rows.data(), sizeof(double) * 18 * n}, {out, sizeof(double) * n}, {info, sizeof(unsigned long long) * n}}, [&](const DevMem* i, const DevMem* o) {
+            const OwConsts* K = i[0].as<OwConsts>();
+            const DevMem &dIn = i[1], &dOut = o[0], &dO = o[1], &dI = o[2];
+            switch (form) {
+                case 0: owdev::k_debug_trem_step<owdev::TSF_LANE><<<grid, block>>>(K, dIn.as<double>(), (int)n, dOut.as<double>(), dO.as<double>(), dI.as<unsigned long long>()); break;
+                case 1: owdev::k_debug_trem_step<owdev::TSF_WIDE><<<grid, block>>>(K, dIn.as<double>(), (int)n, dOut.as<double>(), dO.as<double>(), dI.as<unsigned long long>()); break;
+                default: owdev::k_debug_trem_step<owdev::TSF_ROW><<<grid, block>>>(K, dIn.as<double>(), (int)n, dOut.as<double>(), dO.as<double>(), dI.as<unsigned long long>()); break;
+            }
+        });
         for (size_t c = 0; c < n; ++c)
             for (size_t f = 0; f < 15; ++f) states_out[c * 15 + f] = rows[at(f, c)];
-        return 0;
-    } catch (const std::exception& ex) { (void)hipGetLastError(); set_err(std::string("ow_debug_trem_step: ") + ex.what()); return -1; }
+    });
 }
 int ow_debug_mel_step(int form, double rate, const double* states_in, const double* input, const double* r_ldr, size_t n, double* states_out, double* out,
                       unsigned* info, int device) {
-    try {
+    return debug_hook("ow_debug_mel_step", [&] {
         if (!states_in || !input || !r_ldr || !states_out || !out || !info || form < 0 || form > 6 || !(rate > 0.0)) throw std::runtime_error("bad argument");
-        if (n == 0) return 0;
+        if (n == 0) return;
         if (n > (size_t)1 << 22) throw std::runtime_error("too many cases");
         HIP_OK(hipSetDevice(device));
-        std::unique_ptr<OwConsts> hc(new OwConsts());
-        // build_consts takes the HOST rate; a host rate >= 88.2 kHz runs the chain at that rate without oversampling (engine.rs:195)
-        owhip::build_consts(*hc, rate < 88200.0 ? rate * 0.5 : rate, OW_PREAMP_MELANGE12);
-        if (hc->os_sr != rate) throw std::runtime_error("rate is not reachable as a chain rate");
+        const std::unique_ptr<OwConsts> hc = chain_rate_consts(rate, OW_PREAMP_MELANGE12);
         // the pool launches a form only where the host found its fast path usable (host_pool.inc)
         if (form == 1 && !hc->ml_ok) throw std::runtime_error("the leading block cannot be replayed at this rate");
         if (form >= 3 && !hc->ml_sparse_ok) throw std::runtime_error("the factors do not have the compiled-in pattern at this rate");
@@ -662,36 +639,25 @@ int ow_debug_mel_step(int form, double rate, const double* states_in, const doub
         // engine (col / eng), one [12][12][32] slab per workgroup (lit)
         const size_t lu_ld = 2 * (pairs + 32);
         const size_t lu_doubles = 144 * std::max<size_t>(lu_ld, 32 * (blocks + 1));
-        DevMem dK, dS, dX, dR, dSo, dO, dI, dLu;
-        dK.alloc(sizeof(OwConsts)); dS.alloc(sizeof(double) * 21 * n); dX.alloc(sizeof(double) * n); dR.alloc(sizeof(double) * n);
-        dSo.alloc(sizeof(double) * 21 * n); dO.alloc(sizeof(double) * n); dI.alloc(sizeof(unsigned) * 2 * n); dLu.alloc(sizeof(double) * lu_doubles);
-        HIP_OK(hipMemcpy(dK.p, hc.get(), sizeof(OwConsts), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(dS.p, states_in, sizeof(double) * 21 * n, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(dX.p, input, sizeof(double) * n, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(dR.p, r_ldr, sizeof(double) * n, hipMemcpyHostToDevice));
-        HIP_OK(hipMemset(dSo.p, 0, sizeof(double) * 21 * n));
-        HIP_OK(hipMemset(dO.p, 0, sizeof(double) * n));
-        HIP_OK(hipMemset(dI.p, 0, sizeof(unsigned) * 2 * n));
-        HIP_OK(hipMemset(dLu.p, 0, sizeof(double) * lu_doubles));
+        const size_t d = sizeof(double) * n;
         const dim3 grid((unsigned)blocks), block(64);
-        const OwConsts* K = dK.as<OwConsts>();
+        debug_run({{hc.get(), sizeof(OwConsts)}, {states_in, 21 * d}, {input, d}, {r_ldr, d}},
+                  {{states_out, 21 * d}, {out, d}, {info, sizeof(unsigned) * 2 * n}, {nullptr, sizeof(double) * lu_doubles}}, [&](const DevMem* i, const DevMem* o) {
+            const OwConsts* K = i[0].as<OwConsts>();
+            const DevMem &dS = i[1], &dX = i[2], &dR = i[3], &dSo = o[0], &dO = o[1], &dI = o[2], &dLu = o[3];
 #define OW_MEL_STEP_LAUNCH(F) owdev::k_debug_mel_step<F><<<grid, block>>>(K, dS.as<double>(), dX.as<double>(), dR.as<double>(), (int)n, dSo.as<double>(), \
                                                                          dO.as<double>(), dI.as<unsigned>(), dLu.as<double>(), lu_ld)
-        switch (form) {
-            case 0: OW_MEL_STEP_LAUNCH(owdev::MSF_RANK1); break;
-            case 1: OW_MEL_STEP_LAUNCH(owdev::MSF_LIT_FAST); break;
-            case 2: OW_MEL_STEP_LAUNCH(owdev::MSF_LIT_GENERIC); break;
-            case 3: OW_MEL_STEP_LAUNCH(owdev::MSF_COL_FAST); break;
-            case 4: OW_MEL_STEP_LAUNCH(owdev::MSF_COL_GENERIC); break;
-            case 5: OW_MEL_STEP_LAUNCH(owdev::MSF_ENG_FAST); break;
-            default: OW_MEL_STEP_LAUNCH(owdev::MSF_ENG_GENERIC); break;
-        }
+            switch (form) {
+                case 0: OW_MEL_STEP_LAUNCH(owdev::MSF_RANK1); break;
+                case 1: OW_MEL_STEP_LAUNCH(owdev::MSF_LIT_FAST); break;
+                case 2: OW_MEL_STEP_LAUNCH(owdev::MSF_LIT_GENERIC); break;
+                case 3: OW_MEL_STEP_LAUNCH(owdev::MSF_COL_FAST); break;
+                case 4: OW_MEL_STEP_LAUNCH(owdev::MSF_COL_GENERIC); break;
+                case 5: OW_MEL_STEP_LAUNCH(owdev::MSF_ENG_FAST); break;
+                default: OW_MEL_STEP_LAUNCH(owdev::MSF_ENG_GENERIC); break;
+            }
 #undef OW_MEL_STEP_LAUNCH
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpy(states_out, dSo.p, sizeof(double) * 21 * n, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(out, dO.p, sizeof(double) * n, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(info, dI.p, sizeof(unsigned) * 2 * n, hipMemcpyDeviceToHost));
-        return 0;
-    } catch (const std::exception& ex) { (void)hipGetLastError(); set_err(std::string("ow_debug_mel_step: ") + ex.what()); return -1; }
+        });
+    });
 }
 }  // extern "C"

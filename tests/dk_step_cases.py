@@ -10,6 +10,8 @@ import math
 
 import numpy as np
 
+import step_cases as sc
+
 RATES = (88200.0, 96000.0, 192000.0)            # chain rates: hosts at 44.1 kHz and 48 kHz (oversampled), and at 192 kHz
 _HOST = {88200.0: 44100.0, 96000.0: 48000.0, 192000.0: 192000.0}
 IS, VT, VBE_MAX = 3.03e-14, 0.026, 0.85
@@ -27,22 +29,18 @@ def bjt_ic(v):
     return IS * (math.exp(min(max(v, -1.0), VBE_MAX) / VT) - 1.0)
 
 
-class Cases:
-    """Parallel arrays of one chain rate's cases."""
-
-    def __init__(self, rate):
-        self.rate = rate
-        self.states, self.inputs, self.g, self.gp, self.family = [], [], [], [], []
+class Cases(sc.Cases):
+    """One chain rate's cases, in (main, shadow) pairs."""
+    FAMILIES = FAMILIES
+    COLUMNS = ("inputs", "g", "gp")
 
     def add_pair(self, main, shadow, in_main, in_shadow, g, gp, family):
+        fam = FAMILIES.index(family)
         for st, x in ((main, in_main), (shadow, in_shadow)):
-            self.states.append(np.array(st, dtype=np.float64)); self.inputs.append(float(x)); self.g.append(float(g)); self.gp.append(float(gp))
-            self.family.append(FAMILIES.index(family))
+            self._rows.append((np.array(st, dtype=np.float64), fam, -1, float(x), float(g), float(gp)))
 
     def freeze(self):
-        self.states = np.ascontiguousarray(np.stack(self.states)); self.inputs = np.array(self.inputs); self.g = np.array(self.g)
-        self.gp = np.array(self.gp); self.family = np.array(self.family, dtype=np.int32)
-        self.n = self.states.shape[0]
+        super().freeze()
         assert self.n % 2 == 0 and np.array_equal(self.g[0::2], self.g[1::2]) and np.array_equal(self.gp[0::2], self.gp[1::2])
         return self
 
@@ -185,26 +183,19 @@ def _build_rate(ob, rate):
     return cs.freeze()
 
 
-_CORPUS = None
+corpus = sc.cached(lambda ob: {rate: _build_rate(ob, rate) for rate in RATES})        # {rate: Cases}, built once per process
+V_ROWS = list(range(2, 10)) + [12, 13]               # v[8], v_nl[2]
+I_ROWS = [0, 1, 10, 11]                               # j_cin, cin_rhs_prev, i_nl[2]
 
 
-def corpus(ob):
-    """{rate: Cases}.  Built once per process."""
-    global _CORPUS
-    if _CORPUS is None:
-        _CORPUS = {rate: _build_rate(ob, rate) for rate in RATES}
-    return _CORPUS
+def state_row_ok(a, o, ob):
+    """The state-row bar of test_preamp_state_rows_are_the_references_fields_in_every_chain_kernel, per case: volts within 1e-5 relative +
+    the preamp floor, currents within 1e-5 relative + 1e-12.  a, o: [n][14]."""
+    return sc.within_bar(a, o, ((V_ROWS, ob.ABS_FLOOR_PREAMP), (I_ROWS, 1e-12)))
 
 
-def state_row_ok(a, o, abs_floor_preamp):
-    """The state-row bar of test_preamp_state_rows_are_the_references_fields_in_every_chain_kernel, per case: volts (v[8], v_nl[2]) within
-    1e-5 relative + the preamp floor, currents (j_cin, cin_rhs_prev, i_nl[2]) within 1e-5 relative + 1e-12.  a, o: [n][14]."""
-    with np.errstate(invalid="ignore", over="ignore"):
-        vi = list(range(2, 10)) + [12, 13]
-        ci = [0, 1, 10, 11]
-        volts = np.abs(a[:, vi] - o[:, vi]) <= 1e-5 * np.abs(o[:, vi]) + abs_floor_preamp
-        amps = np.abs(a[:, ci] - o[:, ci]) <= 1e-5 * np.abs(o[:, ci]) + 1e-12
-    return volts.all(axis=1) & amps.all(axis=1)
+def out_ok(a, o, ob):
+    return sc.within_bar(a, o, ((None, ob.ABS_FLOOR_PREAMP),))
 
 
 class Reference:
@@ -214,10 +205,8 @@ class Reference:
         self.states, self.out, self.info = ob.dk_step_cases(cs.rate, cs.states, cs.inputs, cs.g, cs.gp)
         sp, op, _ = ob.dk_step_cases(cs.rate, cs.states, cs.inputs, cs.g, cs.gp, perturbed=True)
         self.finite = np.isfinite(self.states).all(axis=1) & np.isfinite(self.out)
-        with np.errstate(invalid="ignore"):
-            out_ok = np.abs(op - self.out) <= 1e-5 * np.abs(self.out) + ob.ABS_FLOOR_PREAMP
         # comparable: the one-ulp-exp oracle stays within the state-row bar of the unperturbed one (the output is v[OUT], a state row)
-        self.comparable = self.finite & state_row_ok(sp, self.states, ob.ABS_FLOOR_PREAMP) & out_ok
+        self.comparable = self.finite & state_row_ok(sp, self.states, ob) & out_ok(op, self.out, ob)
         upd, ex = self.info[:, 0], self.info[:, 1]
         m = np.zeros((cs.n, N_CLASSES), dtype=bool)
         for u in range(6):
@@ -231,27 +220,10 @@ class Reference:
         self.perturbed_states, self.perturbed_out = sp, op
 
 
-_REFS = None
+references = sc.cached(lambda ob: {rate: Reference(ob, cs) for rate, cs in corpus(ob).items()})
 
 
-def references(ob):
-    global _REFS
-    if _REFS is None:
-        _REFS = {rate: Reference(ob, cs) for rate, cs in corpus(ob).items()}
-    return _REFS
-
-
-def coverage(ob):
-    """Per exit class over all rates: (cases, ill-conditioned among them, comparable among them); then the pair statistics and labels."""
-    refs = references(ob)
-    rows = []
-    for c in range(N_CLASSES):
-        n = sum(int(r.classes[:, c].sum()) for r in refs.values())
-        comp = sum(int((r.classes[:, c] & r.comparable).sum()) for r in refs.values())
-        rows.append((CLASS_NAMES[c], n, n - comp, comp))
-    differ = sum(int((r.info[0::2, 0] != r.info[1::2, 0]).sum()) for r in refs.values())
-    shadow_more = sum(int((r.info[1::2, 0] > r.info[0::2, 0]).sum()) for r in refs.values())
-    return {"classes": rows, "pairs_differ": differ, "pairs_shadow_more": shadow_more,
-            "singular": sum(int(r.singular.sum()) for r in refs.values()),
-            "nonfinite": sum(int((~r.finite).sum()) for r in refs.values()),
-            "cases": sum(r.finite.size for r in refs.values())}
+def pair_statistics(refs):
+    """(pairs whose update counts differ, pairs whose shadow needs more, singular exits) over all rates."""
+    return (sum(int((r.info[0::2, 0] != r.info[1::2, 0]).sum()) for r in refs.values()), sum(int((r.info[1::2, 0] > r.info[0::2, 0]).sum()) for r in refs.values()),
+            sum(int(r.singular.sum()) for r in refs.values()))

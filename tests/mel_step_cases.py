@@ -14,6 +14,8 @@ import math
 
 import numpy as np
 
+import step_cases as sc
+
 RATES = (48000.0, 88200.0, 96000.0, 192000.0)
 CODEGEN_RATE = 48000.0
 R_NOM = 9.99999999999999854e4
@@ -41,72 +43,31 @@ DECISIONS = (1, 3, 4, 5, 10, 13)                         # info columns of the f
                                                         # ringing (either sets the cooldown), forced, NaN reset, the fallback's solve exhausted
 
 
-class Cases:
-    """Parallel arrays of one chain rate's cases, in pair order."""
-
-    def __init__(self, rate):
-        self.rate = rate
-        self._singles = []      # (state, input, r, family, side)
+class Cases(sc.Cases):
+    """One chain rate's cases, in pair order."""
+    FAMILIES = FAMILIES
+    COLUMNS = ("x", "r")
 
     def add(self, state, family, x=0.0, r=None, side=-1):
-        s = np.array(state, dtype=np.float64)
-        self._singles.append((s, float(x), float(s[19]) if r is None else float(r), FAMILIES.index(family), side))
+        super().add(state, family, side, x=x, r=state[19] if r is None else r)
 
     def freeze(self):
         """Pairs: single i is main 2i; its shadow 2i+1 is the state of the next single of the same family (its own for an edge family, so
         that the bisected state stays what it is) with the main's pot and resistance, and input 0."""
+        singles = self._rows         # (state, family, side, x, r); side on mains only
         by_family = {}
-        for i, s in enumerate(self._singles):
-            by_family.setdefault(s[3], []).append(i)
+        for i, s in enumerate(singles):
+            by_family.setdefault(s[1], []).append(i)
         nxt = {}
         for fam, idx in by_family.items():
             edge = FAMILIES[fam].startswith("edge")
             for k, i in enumerate(idx):
                 nxt[i] = i if edge else idx[(k + 1) % len(idx)]
-        st, x, r, fam, side = [], [], [], [], []
-        for i, (s, xi, ri, f, sd) in enumerate(self._singles):
-            sh = self._singles[nxt[i]][0].copy(); sh[19] = s[19]
-            st += [s, sh]; x += [xi, 0.0]; r += [ri, ri]; fam += [f, f]; side += [sd, -1]
-        self.states = np.ascontiguousarray(np.stack(st)); self.x = np.array(x); self.r = np.array(r)
-        self.family = np.array(fam, dtype=np.int32)
-        self.side = np.array(side, dtype=np.int32)       # edge families, mains: 0 = the base's side of the decision, 1 = the other side
-        self.n = self.states.shape[0]
-        del self._singles
-        return self
-
-
-def _bisect_edges(ob, rate, bases, rows, mags_hi, family, cs):
-    """States on either side of one of the step's decisions (trem_step_cases._bisect_edges): row `row` of a base state is moved, and the
-    moved value is bisected between the base's own (info column EDGE_COLUMN[family] as the base has it) and one at which that column is
-    larger, down to NEIGHBOURING doubles of the state row; those two and the next three doubles on either side become cases."""
-    col = EDGE_COLUMN[family]
-    trials = [(b, r, s * m) for b in bases for r in rows for s in (1.0, -1.0) for m in mags_hi]
-    st0 = np.stack([t[0] for t in trials]); row = np.array([t[1] for t in trials]); idx = np.arange(len(trials))
-    lo = st0[idx, row].copy(); hi = lo + np.array([t[2] for t in trials])
-    zero = np.zeros(len(trials))
-
-    def count(x):
-        st = st0.copy(); st[idx, row] = x
-        return ob.melange_step_cases(rate, st, zero, st[:, 19])[2][:, col]
-    c0 = count(lo)
-
-    def f(x):
-        return count(x) > c0
-    ok = f(hi)
-    for _ in range(1100):
-        mid = 0.5 * (lo + hi)
-        stop = (mid == lo) | (mid == hi)
-        if stop.all():
-            break
-        t = f(mid)
-        lo = np.where(~t & ~stop, mid, lo); hi = np.where(t & ~stop, mid, hi)
-    for i in np.nonzero(ok)[0]:
-        for side, (x0, away) in enumerate(((lo[i], -math.inf if hi[i] > lo[i] else math.inf), (hi[i], math.inf if hi[i] > lo[i] else -math.inf))):
-            x = x0
-            for _ in range(4):
-                st = st0[i].copy(); st[row[i]] = x
-                cs.add(st, family, side=side)
-                x = math.nextafter(x, away)
+        self._rows = []
+        for i, (s, f, sd, xi, ri) in enumerate(singles):
+            sh = singles[nxt[i]][0].copy(); sh[19] = s[19]
+            self._rows += [(s, f, sd, xi, ri), (sh, f, -1, 0.0, ri)]
+        return super().freeze()
 
 
 def _build_rate(ob, rate):
@@ -188,7 +149,8 @@ def _build_rate(ob, rate):
                                ("edge: damp", (2, 4, 5, 8, 10), (10.0, 40.0)),
                                ("edge: 1e-4 V threshold", (2, 4, 12, 13, 14), (1e-3, 1e-2)),
                                ("edge: convergence", (2, 4, 5, 13, 14), (1e-3, 1e-2))):
-        _bisect_edges(ob, rate, eb, rows, mags, family, cs)
+        for st, side in sc.bisect_edges(lambda s: ob.melange_step_cases(rate, s, np.zeros(len(s)), s[:, 19])[2][:, EDGE_COLUMN[family]], eb, rows, mags):
+            cs.add(st, family, side=side)
     # far outside anything a circuit does, and non-finite: every row of the state but the cooldown in turn
     for b in (settled, od[17]):
         for row in range(20):
@@ -198,45 +160,32 @@ def _build_rate(ob, rate):
     return cs.freeze()
 
 
-_CORPUS = None
+corpus = sc.cached(lambda ob: {rate: _build_rate(ob, rate) for rate in RATES})        # {rate: Cases}, built once per process
 
 
-def corpus(ob):
-    """{rate: Cases}.  Built once per process."""
-    global _CORPUS
-    if _CORPUS is None:
-        _CORPUS = {rate: _build_rate(ob, rate) for rate in RATES}
-    return _CORPUS
-
-
-def state_row_ok(a, o, floors):
+def state_row_ok(a, o, ob):
     """The state-row bar, per case: the twelve v rows within 1e-5 relative + ABS_FLOOR_MELANGE_STEP_V, the six junction-current rows
-    within 1e-5 relative + ABS_FLOOR_MELANGE_STEP_I, and input_prev, pot and the cooldown EQUAL.  a, o: [n][21]; floors = (volts, amps)."""
-    with np.errstate(invalid="ignore", over="ignore"):
-        volts = np.abs(a[:, V_ROWS] - o[:, V_ROWS]) <= 1e-5 * np.abs(o[:, V_ROWS]) + floors[0]
-        amps = np.abs(a[:, I_ROWS] - o[:, I_ROWS]) <= 1e-5 * np.abs(o[:, I_ROWS]) + floors[1]
-    return volts.all(axis=1) & amps.all(axis=1) & (a[:, 18:] == o[:, 18:]).all(axis=1)
+    within 1e-5 relative + ABS_FLOOR_MELANGE_STEP_I, and input_prev, pot and the cooldown EQUAL.  a, o: [n][21]."""
+    return sc.within_bar(a, o, ((V_ROWS, ob.ABS_FLOOR_MELANGE_STEP_V), (I_ROWS, ob.ABS_FLOOR_MELANGE_STEP_I))) & (a[:, 18:] == o[:, 18:]).all(axis=1)
 
 
-def out_ok(a, o, floors):
-    with np.errstate(invalid="ignore", over="ignore"):
-        return np.abs(a - o) <= 1e-5 * np.abs(o) + floors[0]
+def out_ok(a, o, ob):
+    return sc.within_bar(a, o, ((None, ob.ABS_FLOOR_MELANGE_STEP_V),))
 
 
-# (log_ulp, r_ulp, rebuilt) of the oracle's perturbed variants: the four one-double moves, and -- what differs only at the codegen rate and
-# the nominal pot -- the rebuilt tables in place of the baked ones.  Which of the two such a state runs on is history that a state row
-# does not carry (the reference leaves the baked tables at its first resistance and never returns), the two differ by up to 4.7e-13 of
-# the largest entry (DESIGN.md section 2), and the literal device forms always rebuild: a case is pinned only where both agree.
-VARIANTS = ((1, 0, False), (-1, 0, False), (0, 1, False), (0, -1, False), (0, 0, True))
+# The oracle's perturbed variants: the four one-double moves, and -- what differs only at the codegen rate and the nominal pot -- the
+# rebuilt tables in place of the baked ones.  Which of the two such a state runs on is history that a state row does not carry (the
+# reference leaves the baked tables at its first resistance and never returns), the two differ by up to 4.7e-13 of the largest entry
+# (DESIGN.md section 2), and the literal device forms always rebuild: a case is pinned only where both agree.
+VARIANTS = ({"log_ulp": 1}, {"log_ulp": -1}, {"r_ulp": 1}, {"r_ulp": -1}, {"rebuilt": True})
 
 
 class Reference:
     """The oracle's results on one rate's cases, the exit classes, and which cases the reference algorithm itself pins."""
 
     def __init__(self, ob, cs):
-        floors = (ob.ABS_FLOOR_MELANGE_STEP_V, ob.ABS_FLOOR_MELANGE_STEP_I)
         self.states, self.out, self.info = ob.melange_step_cases(cs.rate, cs.states, cs.x, cs.r)
-        self.perturbed = [ob.melange_step_cases(cs.rate, cs.states, cs.x, cs.r, log_ulp=lu, r_ulp=ru, rebuilt=rb) for lu, ru, rb in VARIANTS]
+        self.perturbed = [ob.melange_step_cases(cs.rate, cs.states, cs.x, cs.r, **v) for v in VARIANTS]
         f = self.info
         self.nan_reset = f[:, 10] > 0
         # finite: the state going in and everything coming out (a non-finite input or resistance is one of the step's guarded exits)
@@ -248,7 +197,7 @@ class Reference:
         for sp, op, fp in self.perturbed:
             same = (fp[:, DECISIONS] == f[:, DECISIONS]).all(axis=1)
             self.keeps &= same
-            comp &= same & state_row_ok(sp, self.states, floors) & out_ok(op, self.out, floors)
+            comp &= same & state_row_ok(sp, self.states, ob) & out_ok(op, self.out, ob)
         self.comparable = comp
         m = np.zeros((cs.n, N_CLASSES), dtype=bool)
         trap_kept = f[:, 1] == 0
@@ -274,24 +223,4 @@ class Reference:
         self.classes = m
 
 
-_REFS = None
-
-
-def references(ob):
-    global _REFS
-    if _REFS is None:
-        _REFS = {rate: Reference(ob, cs) for rate, cs in corpus(ob).items()}
-    return _REFS
-
-
-def coverage(ob):
-    """Per exit class over all rates: (name, cases, comparable among them); the finite cases and the non-comparable ones among them."""
-    refs = references(ob)
-    rows = []
-    for c in range(N_CLASSES):
-        n = sum(int(r.classes[:, c].sum()) for r in refs.values())
-        comp = sum(int((r.classes[:, c] & r.comparable).sum()) for r in refs.values())
-        rows.append((CLASS_NAMES[c], n, comp))
-    fin = sum(int(r.finite.sum()) for r in refs.values())
-    return {"classes": rows, "finite": fin, "ill": fin - sum(int(r.comparable.sum()) for r in refs.values()),
-            "cases": sum(r.finite.size for r in refs.values())}
+references = sc.cached(lambda ob: {rate: Reference(ob, cs) for rate, cs in corpus(ob).items()})

@@ -6,6 +6,7 @@ import numpy as np
 
 import dk_step_cases as dk
 import oracle_binding as ob
+import step_cases as sc
 
 
 def test_step_entry_is_the_engines_own_step():
@@ -50,24 +51,21 @@ def test_corpus_reaches_every_exit_and_the_reference_pins_it():
     and 300 000 random pairs, as the opening state of a step (the first sweep's 2x2 is formed at exactly those voltages), plus every case
     of the corpus.  det = (1 - k00 gm0)(1 - k11 gm1) - k01 k10 gm0 gm1 is 1 when both junctions are off and a sum of O(1) .. O(1e9) terms
     otherwise; |det| < 1e-30 would need them to cancel to 100 bits."""
-    cov = dk.coverage(ob)
+    refs = dk.references(ob)
+    cov = sc.coverage(refs, dk.CLASS_NAMES)
+    differ, shadow_more, singular = dk.pair_statistics(refs)
     print()
     print("dk_step corpus: %d cases (%s per rate)" % (cov["cases"], ", ".join("%d" % cs.n for cs in dk.corpus(ob).values())))
-    for name, n, ill, comp in cov["classes"]:
-        print("  %-26s %6d cases  ill-conditioned %5d (%.2f %%)  comparable %6d" % (name, n, ill, 100.0 * ill / max(n, 1), comp))
+    for name, n, comp in cov["classes"]:
+        print("  %-26s %6d cases  ill-conditioned %5d (%.2f %%)  comparable %6d" % (name, n, n - comp, 100.0 * (n - comp) / max(n, 1), comp))
     print("  pairs whose update counts differ: %d, shadow needs more: %d; singular exits: %d; non-finite results: %d"
-          % (cov["pairs_differ"], cov["pairs_shadow_more"], cov["singular"], cov["nonfinite"]))
-    for name, n, ill, comp in cov["classes"]:
-        assert n >= dk.MIN_CLASS, (name, n)
-        assert ill <= dk.MAX_ILL_SHARE * n, (name, n, ill)
-        assert comp >= dk.MIN_COMPARABLE, (name, comp)
-    assert cov["pairs_differ"] >= 256 and cov["pairs_shadow_more"] >= 64, cov
-    assert cov["nonfinite"] >= 1
-    refs = dk.references(ob)
+          % (differ, shadow_more, singular, cov["cases"] - cov["finite"]))
+    sc.check_coverage(dk, ob, ill_per_class=True)
+    assert differ >= 256 and shadow_more >= 64, (differ, shadow_more)
+    assert cov["cases"] - cov["finite"] >= 1
     for rate, cs in dk.corpus(ob).items():
-        assert set(np.unique(cs.family)) == set(range(len(dk.FAMILIES))), (rate, np.unique(cs.family))
         r = refs[rate]
-        assert not (r.classes[~r.finite]).any() and not r.comparable[~r.finite].any()
+        assert not (r.classes[~r.finite]).any()
         # the clamp edges and the tolerance edge are really straddled
         edge = cs.family == dk.FAMILIES.index("junction edge")
         vn = cs.states[edge][:, 12:14]

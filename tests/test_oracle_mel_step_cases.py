@@ -9,6 +9,7 @@ import numpy as np
 
 import oracle_binding as ob
 import mel_step_cases as mc
+import step_cases as sc
 
 
 def test_step_entry_is_the_solvers_own_step():
@@ -70,36 +71,20 @@ def test_corpus_reaches_every_exit_and_the_reference_pins_it():
     below 1e-15 needs the elimination to cancel to 50 bits, which no state was found to produce.  Searched (singular_search below):
     40 000 random multi-row kicks of 1 mV .. 30 V / 1 uA .. 30 mA per rate at random resistances on top of the corpus.  No case was
     invented; the test fails if one turns up, so that it is then added."""
-    cov = mc.coverage(ob)
+    cov = sc.coverage(mc.references(ob), mc.CLASS_NAMES)
     print()
     print("mel_step corpus: %d cases (%s per rate), %d finite, %d of them not comparable (%.3f %%)" % (
         cov["cases"], ", ".join("%d" % cs.n for cs in mc.corpus(ob).values()), cov["finite"], cov["ill"], 100.0 * cov["ill"] / cov["finite"]))
     for name, n, comp in cov["classes"]:
         print("  %-30s %6d cases  comparable %6d" % (name, n, comp))
     print("  floors (oracle_binding): %.1e V, %.1e A" % (ob.ABS_FLOOR_MELANGE_STEP_V, ob.ABS_FLOOR_MELANGE_STEP_I))
-    for c, (name, n, comp) in enumerate(cov["classes"]):
-        if c == mc.SINGULAR:
-            assert n == 0, "a singular sweep exists: give the class its minimum"
-            continue
-        assert n >= mc.MIN_CLASS, (name, n)
-        assert comp >= mc.MIN_COMPARABLE, (name, comp)
-    assert cov["ill"] <= mc.MAX_ILL_SHARE * cov["finite"], cov
+    sc.check_coverage(mc, ob, empty=(mc.CLASS_NAMES[mc.SINGULAR],))
     refs = mc.references(ob)
     assert mc.CODEGEN_RATE in refs and len(refs) >= 4
     sweeps = set()
     for rate, cs in mc.corpus(ob).items():
         r = refs[rate]
-        assert set(np.unique(cs.family)) == set(range(len(mc.FAMILIES))), (rate, np.unique(cs.family))
-        assert not r.comparable[~r.finite].any()
         sweeps |= set(r.info[r.info[:, 1] == 0, 0].tolist())
-        # both sides of each bisected decision are present, and the boundary pairs (the first case of each side) differ in the column
-        for fam, col in mc.EDGE_COLUMN.items():
-            m = cs.family == mc.FAMILIES.index(fam)
-            lo = np.nonzero(m & (cs.side == 0))[0][0::4]; hi = np.nonzero(m & (cs.side == 1))[0][0::4]
-            assert lo.size >= 4 and lo.size == hi.size, (rate, fam, lo.size, hi.size)
-            assert (r.info[hi, col] > r.info[lo, col]).all(), (rate, fam)
-            d = np.abs(cs.states[hi] - cs.states[lo])
-            assert ((d > 0).sum(axis=1) == 1).all() and (np.nextafter(cs.states[lo], cs.states[hi]) == cs.states[hi]).all(), (rate, fam)
         # non-finite voltages, currents and input_prev all end in the reset (an infinite pot is a conductance of zero: the step goes
         # through); non-finite inputs and resistances never do on their own
         ext = cs.family == mc.FAMILIES.index("extreme")

@@ -5,6 +5,7 @@ unperturbed one).  tests/test_gpu_trem_step.py compares the kernels on exactly t
 import numpy as np
 
 import oracle_binding as ob
+import step_cases as sc
 import trem_step_cases as tc
 
 
@@ -51,36 +52,20 @@ def test_corpus_reaches_every_exit_and_the_reference_pins_it():
     of two others) cancels the rest: below 1e-15 needs a cancellation to 50 bits that no state was found to produce.  Searched
     (singular_search below): 60 000 random multi-row kicks of 1 mV .. 30 V / 1 uA .. 30 mA per rate on top of the corpus.  No case was
     invented; the test fails if one turns up, so that it is then added."""
-    cov = tc.coverage(ob)
+    cov = sc.coverage(tc.references(ob), tc.CLASS_NAMES)
     print()
     print("trem_step corpus: %d cases (%s per rate), %d finite, %d of them not comparable (%.3f %%)" % (
         cov["cases"], ", ".join("%d" % cs.n for cs in tc.corpus(ob).values()), cov["finite"], cov["ill"], 100.0 * cov["ill"] / cov["finite"]))
     for name, n, comp in cov["classes"]:
         print("  %-26s %6d cases  comparable %6d" % (name, n, comp))
     print("  floors (oracle_binding): %.1e V, %.1e A" % (ob.ABS_FLOOR_TREM_STEP_V, ob.ABS_FLOOR_TREM_STEP_I))
-    for c, (name, n, comp) in enumerate(cov["classes"]):
-        if name == "singular sweep":
-            assert n == 0, "a singular sweep exists: give the class its minimum"
-            continue
-        assert n >= tc.MIN_CLASS, (name, n)
-        assert comp >= tc.MIN_COMPARABLE, (name, comp)
-    assert cov["ill"] <= tc.MAX_ILL_SHARE * cov["finite"], cov
+    sc.check_coverage(tc, ob, empty=("singular sweep",))
     refs = tc.references(ob)
     assert tc.CODEGEN_RATE in refs and len(refs) >= 4
     iters = set()
     for rate, cs in tc.corpus(ob).items():
         r = refs[rate]
-        assert set(np.unique(cs.family)) == set(range(len(tc.FAMILIES))), (rate, np.unique(cs.family))
-        assert not r.comparable[~r.finite].any()
         iters |= set(r.info[(r.info[:, 1] == 0), 0].tolist())
-        # both sides of each bisected decision are present, and the boundary pairs (the first case of each side) differ in the column
-        for fam, col in tc.EDGE_COLUMN.items():
-            m = cs.family == tc.FAMILIES.index(fam)
-            lo = np.nonzero(m & (cs.side == 0))[0][0::4]; hi = np.nonzero(m & (cs.side == 1))[0][0::4]
-            assert lo.size >= 4 and lo.size == hi.size, (rate, fam, lo.size, hi.size)
-            assert (r.info[hi, col] > r.info[lo, col]).all(), (rate, fam)
-            d = np.abs(cs.states[hi] - cs.states[lo])
-            assert ((d > 0).sum(axis=1) == 1).all() and (np.nextafter(cs.states[lo], cs.states[hi]) == cs.states[hi]).all(), (rate, fam)
         # the non-finite kicks all end in the reset
         ext = cs.family == tc.FAMILIES.index("extreme")
         assert r.nan_reset[ext & ~np.isfinite(cs.states).all(axis=1)].all()

@@ -12,6 +12,8 @@ import math
 
 import numpy as np
 
+import step_cases as sc
+
 RATES = (48000.0, 88200.0, 96000.0, 192000.0)
 CODEGEN_RATE = 48000.0
 N_CLASSES = 10
@@ -25,6 +27,8 @@ I_KICKS = np.logspace(-9.0, math.log10(4e-2), 12)       # amps: one junction cur
 MIN_CLASS = 256                                         # (dk_step_cases.MIN_CLASS)
 MIN_COMPARABLE = 64
 MAX_ILL_SHARE = 0.10
+VARIANTS = ({"log_ulp": 1}, {"log_ulp": -1})            # the oracle's perturbed variants: pnjlim's logarithm one double away, either way
+DECISIONS = [1, 3, 4]                                   # info columns of the exits a perturbed oracle has to keep: retry taken, converged, NaN reset
 # the three kicks of test_gpu_trajectory.py::test_row_oscillator_kernels_equal_the_quad_lane_kernels (added to DC_OP, rows 0..14)
 TRAJECTORY_KICKS = (np.array([0, 0, 2.0, 0, -1.5, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0]),
                     np.array([-6.0, 3.0, 0, 4.0, 5.0, 0, 0.5, 1e-3, -1e-3, 2e-3, 1e-3, 0, 0, 0, 0.0]),
@@ -39,57 +43,8 @@ def dc_op(ob):
     return so[0].copy()
 
 
-class Cases:
-    """Parallel arrays of one chain rate's cases."""
-
-    def __init__(self, rate):
-        self.rate = rate
-        self.states, self.family, self.side = [], [], []
-
-    def add(self, state, family, side=-1):
-        self.states.append(np.array(state, dtype=np.float64)); self.family.append(FAMILIES.index(family)); self.side.append(side)
-
-    def freeze(self):
-        self.states = np.ascontiguousarray(np.stack(self.states)); self.family = np.array(self.family, dtype=np.int32)
-        self.side = np.array(self.side, dtype=np.int32)       # edge families: 0 = the base's side of the decision, 1 = the other side
-        self.n = self.states.shape[0]
-        return self
-
-
-def _bisect_edges(ob, rate, bases, rows, mags_hi, family, cs):
-    """States on either side of one of the step's decisions: row `row` of a base state is moved, and the moved value is bisected between the
-    base's own (info column EDGE_COLUMN[family] as the base has it) and one at which that column is larger, down to NEIGHBOURING doubles of
-    the state row; those two and the next three doubles on either side become cases.  Every (base, row, sign, starting magnitude) is tried;
-    the ones whose ends differ are kept."""
-    col = EDGE_COLUMN[family]
-    trials = [(b, r, s * m) for b in bases for r in rows for s in (1.0, -1.0) for m in mags_hi]
-    st0 = np.stack([t[0] for t in trials]); row = np.array([t[1] for t in trials]); idx = np.arange(len(trials))
-    lo = st0[idx, row].copy(); hi = lo + np.array([t[2] for t in trials])
-
-    def count(x):
-        st = st0.copy(); st[idx, row] = x
-        return ob.trem_step_cases(rate, st)[2][:, col]
-    c0 = count(lo)
-
-    def f(x):
-        return count(x) > c0
-    ok = f(hi)
-    for _ in range(1100):
-        mid = 0.5 * (lo + hi)
-        stop = (mid == lo) | (mid == hi)
-        if stop.all():
-            break
-        t = f(mid)
-        lo = np.where(~t & ~stop, mid, lo); hi = np.where(t & ~stop, mid, hi)
-    n_added = 0
-    for i in np.nonzero(ok)[0]:
-        for side, (x0, away) in enumerate(((lo[i], -math.inf if hi[i] > lo[i] else math.inf), (hi[i], math.inf if hi[i] > lo[i] else -math.inf))):
-            x = x0
-            for _ in range(4):
-                st = st0[i].copy(); st[row[i]] = x
-                cs.add(st, family, side); n_added += 1
-                x = math.nextafter(x, away)
-    return n_added
+class Cases(sc.Cases):
+    FAMILIES = FAMILIES
 
 
 def _build_rate(ob, rate):
@@ -145,7 +100,8 @@ def _build_rate(ob, rate):
                                ("edge: 1e-4 V threshold", (0, 2, 4, 8), (1e-3, 1e-2)),
                                ("edge: pnjlim", (2, 4, 0), (0.5, 5.0)),
                                ("edge: 3.5 V cap", (0, 2, 4, 3), (20.0, 40.0))):
-        _bisect_edges(ob, rate, eb, rows, mags, family, cs)
+        for st, side in sc.bisect_edges(lambda s: ob.trem_step_cases(rate, s)[2][:, EDGE_COLUMN[family]], eb, rows, mags):
+            cs.add(st, family, side)
     # far outside anything a circuit does, and non-finite: every row of the state in turn
     for b in (dc, settled[0], settled[40]):
         for row in range(15):
@@ -155,44 +111,36 @@ def _build_rate(ob, rate):
     return cs.freeze()
 
 
-_CORPUS = None
+corpus = sc.cached(lambda ob: {rate: _build_rate(ob, rate) for rate in RATES})        # {rate: Cases}, built once per process
+V_ROWS = slice(0, 7)
+I_ROWS = slice(7, 15)
 
 
-def corpus(ob):
-    """{rate: Cases}.  Built once per process."""
-    global _CORPUS
-    if _CORPUS is None:
-        _CORPUS = {rate: _build_rate(ob, rate) for rate in RATES}
-    return _CORPUS
+def groups(ob):
+    """The state-row bar's groups: volts (v[7]) within 1e-5 relative + ABS_FLOOR_TREM_STEP_V, amps (i_prev[4], i_pp[4]) within 1e-5
+    relative + ABS_FLOOR_TREM_STEP_I."""
+    return ((V_ROWS, ob.ABS_FLOOR_TREM_STEP_V), (I_ROWS, ob.ABS_FLOOR_TREM_STEP_I))
 
 
-def state_row_ok(a, o, floors):
-    """The state-row bar, per case: volts (v[7]) within 1e-5 relative + ABS_FLOOR_TREM_STEP_V, amps (i_prev[4], i_pp[4]) within 1e-5
-    relative + ABS_FLOOR_TREM_STEP_I.  a, o: [n][15]; floors = (volts, amps)."""
-    with np.errstate(invalid="ignore", over="ignore"):
-        volts = np.abs(a[:, :7] - o[:, :7]) <= 1e-5 * np.abs(o[:, :7]) + floors[0]
-        amps = np.abs(a[:, 7:] - o[:, 7:]) <= 1e-5 * np.abs(o[:, 7:]) + floors[1]
-    return volts.all(axis=1) & amps.all(axis=1)
+def state_row_ok(a, o, ob):
+    return sc.within_bar(a, o, groups(ob))
 
 
-def floor_governed(a, o, floors):
-    """(volts, amps): the largest |a - o| over the finite rows whose tolerance in state_row_ok is governed by the floor rather than by the
-    relative term (1e-5 |o| < floor) -- what a floor has to cover."""
-    with np.errstate(invalid="ignore", over="ignore"):
-        d = np.abs(a - o)
-        fin = np.isfinite(a) & np.isfinite(o)
-        gv = fin[:, :7] & (1e-5 * np.abs(o[:, :7]) < floors[0])
-        ga = fin[:, 7:] & (1e-5 * np.abs(o[:, 7:]) < floors[1])
-    return (float(d[:, :7][gv].max()) if gv.any() else 0.0), (float(d[:, 7:][ga].max()) if ga.any() else 0.0)
+def out_ok(a, o, ob):
+    return sc.within_bar(a, o, ((None, ob.ABS_FLOOR_TREM_STEP_V),))
+
+
+def floor_governed(a, o, ob):
+    """(volts, amps): what the two floors have to cover (step_cases.floor_governed)."""
+    return sc.floor_governed(a, o, groups(ob))
 
 
 class Reference:
     """The oracle's results on one rate's cases, the exit classes, and which cases the reference algorithm itself pins."""
 
     def __init__(self, ob, cs):
-        floors = (ob.ABS_FLOOR_TREM_STEP_V, ob.ABS_FLOOR_TREM_STEP_I)
         self.states, self.out, self.info = ob.trem_step_cases(cs.rate, cs.states)
-        self.perturbed = [ob.trem_step_cases(cs.rate, cs.states, log_ulp=u) for u in (1, -1)]
+        self.perturbed = [ob.trem_step_cases(cs.rate, cs.states, **v) for v in VARIANTS]
         f = self.info
         self.nan_reset = f[:, 4] > 0
         self.finite = np.isfinite(cs.states).all(axis=1) & np.isfinite(self.states).all(axis=1) & np.isfinite(self.out)
@@ -200,7 +148,7 @@ class Reference:
         # reset) and stays within the state-row bar of the unperturbed one (the output is v[OUT], a state row)
         comp = self.finite.copy()
         for sp, op, fp in self.perturbed:
-            comp &= state_row_ok(sp, self.states, floors) & (fp[:, [1, 3, 4]] == f[:, [1, 3, 4]]).all(axis=1)
+            comp &= state_row_ok(sp, self.states, ob) & (fp[:, DECISIONS] == f[:, DECISIONS]).all(axis=1)
         self.comparable = comp
         self.no_log = f[:, 7] == 0                          # no pnjlim logarithm in the step: nothing but IEEE operations
         m = np.zeros((cs.n, N_CLASSES), dtype=bool)
@@ -219,24 +167,4 @@ class Reference:
         self.classes = m
 
 
-_REFS = None
-
-
-def references(ob):
-    global _REFS
-    if _REFS is None:
-        _REFS = {rate: Reference(ob, cs) for rate, cs in corpus(ob).items()}
-    return _REFS
-
-
-def coverage(ob):
-    """Per exit class over all rates: (name, cases, comparable among them); the finite cases and the non-comparable ones among them."""
-    refs = references(ob)
-    rows = []
-    for c in range(N_CLASSES):
-        n = sum(int(r.classes[:, c].sum()) for r in refs.values())
-        comp = sum(int((r.classes[:, c] & r.comparable).sum()) for r in refs.values())
-        rows.append((CLASS_NAMES[c], n, comp))
-    fin = sum(int(r.finite.sum()) for r in refs.values())
-    return {"classes": rows, "finite": fin, "ill": fin - sum(int(r.comparable.sum()) for r in refs.values()),
-            "cases": sum(r.finite.size for r in refs.values())}
+references = sc.cached(lambda ob: {rate: Reference(ob, cs) for rate, cs in corpus(ob).items()})
