@@ -867,6 +867,35 @@ typedef struct ow_pump_row {
  * capture < 2 with OW_PUMP_RAMP, an unknown schedule, an extra_sample other than 0 or 1, a run of 2^40 samples or more, a short trace_stride, null arguments. */
 int ow_pump_measure(const ow_pump_point* points, size_t n, const ow_pump_cfg* cfg, ow_pump_row* rows_out, double* trace_out, size_t trace_stride);
 
+/* ---- recorded notes against renders (tools/wurli_compare.py) ------------------------------------------------------------------- */
+/* compute_stft (:46-58) and what its two callers take from S (harmonic_profile :61-78, measure_spectral_centroid :122-127), for many
+ * clips per call.  clips: f64 [n_clips][stride] (a device pointer if clips_is_device != 0, e.g. what ow_batch_render left in HBM);
+ * lengths[c] <= stride valid samples; wav24_mode as for ow_extract_harmonics.  Per clip: n_frames = max(1, floor((len - n_fft) / hop) + 1)
+ * (Python's floor: one frame when len < n_fft), frame i = samples [i * hop, i * hop + n_fft), zero-padded past len; the analysis reads
+ * nothing at or beyond lengths[c].
+ * mean_mag: host f64 [n_clips][n_fft / 2 + 1] or NULL: the mean over the frames of |rfft(frame * window)|, frames added in ascending order.
+ * centroid: host f64 [n_clips] or NULL: the mean over the frames of sum_k f_k |X_k|^2 / (sum_k |X_k|^2 + 1e-10), f_k = k * (1 / (n_fft *
+ * (1 / sample_rate))), numpy's rfftfreq.  At least one of the two is given.
+ * window: host f64 [n_fft], the caller's: np.hanning(n_fft).astype(float32) widened, so its bits are the host libm's, as those of the
+ * library's own Hann tables are.
+ * Arithmetic: the reference holds float32, so a sample is rounded to float32 (after the 24-bit quantiser, if any) and frame * window is one
+ * rounded float32 product; from there on f64: an n_fft / 2-point complex FFT in LDS with twiddles from exact integer phases, fixed
+ * summation orders, no atomics.  A clip's numbers do not depend on the other clips of the call or on the chunking (1 GiB of device
+ * memory per chunk for rows copied from the host and per-frame magnitudes).
+ * Returns 0, <0 on error.  Refused (ow_last_error says why), never clamped: a null argument, an n_fft that is not a power of two in 64..8192,
+ * hop == 0, an unknown wav24_mode, a sample rate that is not finite and positive, a length beyond the stride, a clip that alone exceeds the
+ * chunk's memory.  n_clips == 0 returns 0. */
+int ow_stft_profile(const double* clips, size_t n_clips, size_t stride, const uint32_t* lengths, const double* window, uint32_t n_fft, uint32_t hop,
+                    double sample_rate, int wav24_mode, int device, int clips_is_device, double* mean_mag, double* centroid);
+/* The RMS envelopes of measure_decay (:95-107; 2048 / 512) and measure_attack_time (:136-147; 1024 / 128) and the sum of measure_rms
+ * (:130-133) on the same kind of rows, the same float32 rounding of a sample, squares and sums in f64: rms: host f64 [n_clips][frames_stride],
+ * rms[c][i] = sqrt(sum of the squares of frame i (zero-padded past len) / frame_len) for i < n_frames[c] = max(1, floor((len - frame_len) /
+ * hop) + 1), 0.0 beyond; n_frames: host [n_clips]; sum_sq: host f64 [n_clips] (the squares of the whole clip) or NULL.
+ * Returns 0, <0 on error.  Refused: a null argument, frame_len == 0, hop == 0, an unknown wav24_mode, a length beyond the stride, a
+ * frames_stride smaller than a clip's frame count.  n_clips == 0 returns 0. */
+int ow_frame_rms(const double* clips, size_t n_clips, size_t stride, const uint32_t* lengths, uint32_t frame_len, uint32_t hop, int wav24_mode,
+                 int device, int clips_is_device, double* rms, size_t frames_stride, uint32_t* n_frames, double* sum_sq);
+
 #ifdef __cplusplus
 }
 #endif

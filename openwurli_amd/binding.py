@@ -436,6 +436,8 @@ SYMBOLS = {
     "ow_overshoot": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwOvershootCfg), _VP, _VP, C.c_size_t]),
     "ow_bark_audit": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwBarkCfg), _VP, _VP, C.c_size_t]),
     "ow_pump_measure": (C.c_int, [_VP, C.c_size_t, C.POINTER(OwPumpCfg), _VP, _VP, C.c_size_t]),
+    "ow_stft_profile": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, _VP, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int, _VP, _VP]),
+    "ow_frame_rms": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP, _VP]),
 }
 
 
