@@ -867,6 +867,46 @@ typedef struct ow_pump_row {
  * capture < 2 with OW_PUMP_RAMP, an unknown schedule, an extra_sample other than 0 or 1, a run of 2^40 samples or more, a short trace_stride, null arguments. */
 int ow_pump_measure(const ow_pump_point* points, size_t n, const ow_pump_cfg* cfg, ow_pump_row* rows_out, double* trace_out, size_t trace_stride);
 
+/* ---- the pump-dynamics fitter (tools/analyze_pump_dynamics.py) ------------------------------------------------------------------ */
+/* Six cheap predictors R(t) -> pump(t) over the static pump table of `pump-sweep`, fitted to slewed-R captures of `pump-sinusoid` by
+ * Nelder-Mead.  Plain scalars and pointers only (no record).
+ * Traces: r / target are host f64, concatenated; trace t is samples offsets[t] .. offsets[t + 1] (offsets: n_traces + 1 entries,
+ * offsets[0] == 0) at sample_rates[t].  Table: lut_r strictly ascending and positive, lut_v, 2 <= n_lut <= 1024 points;
+ * the lookup is numpy.interp on ln(clip(x, lut_r[0], lut_r[n_lut - 1])) over ln(lut_r): slope * offset + the left value, exact on a
+ * knot, the ends held.
+ * Models (parameters in rows of four doubles, the first 1 / 1 / 2 / 2 / 3 / 4 used), a = 1 - exp(-1 / (sr tau_ms 1e-3)):
+ *   0 lpf_R      [tau_ms]            s[0] = R[0], s[n] = s[n-1] + a (R[n] - s[n-1]); pred = table(s);           tau_ms <= 0: invalid
+ *   1 lpf_lnR    [tau_ms]            the same on ln R; pred = table(exp(s))
+ *   2 iir1_dR    [a, b]              xi[0] = 0, xi[n] = a xi[n-1] + b (R[n] - R[n-1]); pred = table(R) + xi;    a outside [0, 1): invalid
+ *   3 iir1_dlnR  [a, b]              the same driven by ln R[n] - ln R[n-1]
+ *   4 iir1_asym  [a, b_up, b_dn]     the same with b_up where the drive is positive, b_dn elsewhere
+ *   5 iir2_dlnR  [a1, a2, b0, b1]    xi[0] = xi[1] = 0, xi[n] = a1 xi[n-1] + a2 xi[n-2] + b0 u[n] + b1 u[n-1], u[n] = ln R[n] - ln R[n-1];
+ *                                    invalid unless both roots of z^2 - a1 z - a2 are inside the unit circle (the reference's test)
+ * Loss: 1e9 for an invalid vector or a prediction that is not finite at every sample; else 1000 sqrt(mean(d d)) over samples skip .. n
+ * (mV; the reference's skip is 200), d d summed in sample order.  Every stated operation is one IEEE operation in the reference's
+ * order; exp and log are the device library's.
+ * Refused with <0 before any launch, the outputs untouched (ow_last_error says why): a trace of skip + 1 samples or fewer, a table that is
+ * not strictly ascending or too small / large, a non-positive R, a model id above 5, a trace index out of range, a non-finite input
+ * (samples, rates, table, used parameters), maxiter == 0, a short pred_stride, null arguments. */
+/* Plain numbers, no new constants (the ABI version stands).  The table holds at most 1024 points.  A fit's status is
+ *   0  converged: both of scipy's termination tests passed
+ *   1  maxiter: nit reached maxiter
+ *   2  start invalid: the whole start simplex was invalid and no valid point was ever found; fun is 1e9 (scipy reports success) */
+/* loss_out: host f64 [n_evals]; pred_out: NULL or host f64 [n_evals][pred_stride >= the evaluation's trace]: the prediction rows (NaN
+ * rows for an invalid vector; 0 beyond the trace).  An evaluation's numbers do not depend on the other evaluations of the call. */
+int ow_pump_fit_eval(const double* r, const double* target, const uint64_t* offsets, const double* sample_rates, size_t n_traces, const double* lut_r,
+                     const double* lut_v, size_t n_lut, const uint32_t* eval_trace, const uint32_t* eval_model, const double* eval_params, size_t n_evals,
+                     uint32_t skip, int device, double* loss_out, double* pred_out, size_t pred_stride);
+/* scipy.optimize.minimize(method="Nelder-Mead", options={xatol, fatol, maxiter}) per fit, from x0 [n_fits][4]: the start simplex scales
+ * each coordinate by 1.05 (0.00025 where it is zero); rho 1, chi 2, psi = sigma 0.5; scipy's termination tests and acceptance
+ * inequalities; a stable ordering; maxfun unbounded; vertex arithmetic in scipy's operation order.  Outputs by fit: x_out [n_fits][4]
+ * (0 beyond the model's parameters), fun_out, nit_out, nfev_out (as scipy counts them), status_out (0 / 1 / 2, above).  A fit's result does
+ * not depend on the other fits of the call or on their order. */
+int ow_pump_fit(const double* r, const double* target, const uint64_t* offsets, const double* sample_rates, size_t n_traces, const double* lut_r,
+                const double* lut_v, size_t n_lut, const uint32_t* fit_trace, const uint32_t* fit_model, const double* x0, size_t n_fits, uint32_t skip,
+                double xatol, double fatol, uint32_t maxiter, int device, double* x_out, double* fun_out, uint32_t* nit_out, uint32_t* nfev_out,
+                uint32_t* status_out);
+
 /* ---- recorded notes against renders (tools/wurli_compare.py) ------------------------------------------------------------------- */
 /* compute_stft (:46-58) and what its two callers take from S (harmonic_profile :61-78, measure_spectral_centroid :122-127), for many
  * clips per call.  clips: f64 [n_clips][stride] (a device pointer if clips_is_device != 0, e.g. what ow_batch_render left in HBM);

@@ -306,6 +306,10 @@ class OwPumpRow(C.Structure):
                [(f, C.c_uint64) for f in ("nr_exhausted", "be_fallbacks", "voltage_damps", "nan_resets")]
 
 
+PUMP_FIT_MAX_LUT = 1024                                                           # include/openwurli_hip.h: ow_pump_fit's table limit
+PUMP_FIT_CONVERGED, PUMP_FIT_MAXITER, PUMP_FIT_START_INVALID = 0, 1, 2            # its status codes
+
+
 class OwSegment(C.Structure):
     _fields_ = [("row", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("n_harmonics", C.c_uint32), ("f0", C.c_double)]
 
@@ -436,6 +440,9 @@ SYMBOLS = {
     "ow_overshoot": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwOvershootCfg), _VP, _VP, C.c_size_t]),
     "ow_bark_audit": (C.c_longlong, [_VP, C.c_size_t, C.POINTER(OwBarkCfg), _VP, _VP, C.c_size_t]),
     "ow_pump_measure": (C.c_int, [_VP, C.c_size_t, C.POINTER(OwPumpCfg), _VP, _VP, C.c_size_t]),
+    "ow_pump_fit_eval": (C.c_int, [_VP, _VP, _VP, _VP, C.c_size_t, _VP, _VP, C.c_size_t, _VP, _VP, _VP, C.c_size_t, C.c_uint32, C.c_int, _VP, _VP, C.c_size_t]),
+    "ow_pump_fit": (C.c_int, [_VP, _VP, _VP, _VP, C.c_size_t, _VP, _VP, C.c_size_t, _VP, _VP, _VP, C.c_size_t, C.c_uint32, C.c_double, C.c_double,
+                              C.c_uint32, C.c_int, _VP, _VP, _VP, _VP, _VP]),
     "ow_stft_profile": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, _VP, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int, _VP, _VP]),
     "ow_frame_rms": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP, _VP]),
 }
