@@ -677,7 +677,7 @@ static bool launch_chain(ow_pool* p, const Block& b, ChainKernel kernel) {
     const int I = (int)p->I, L = b.L, Lcap = (int)p->Lcap, e0 = b.e0, ne = b.ne;
     hipStream_t s = p->stream;
     const owdev::OwTremSrc& tsrc = b.tsrc;
-    const dim3 per8((ne + 7) / 8), per32((ne + 31) / 32), per64((ne + 63) / 64);
+    const dim3 per8((ne + 7) / 8), per32((ne + 31) / 32), per64((ne + 63) / 64), per512((ne + 511) / 512);   // per512: eight wavefronts of 64 engines (ow_wave_turns.h)
     const int generic = p->sw.mel_generic ? 1 : 0;
     switch (kernel) {
     case CHAIN_NONE: break;
@@ -701,7 +701,7 @@ static bool launch_chain(ow_pool* p, const Block& b, ChainKernel kernel) {
         break;
     case PREAMP_MEL: owdev::k_preamp_mel<<<per32, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_mel_settled, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, p->d_noise, I, L, Lcap, e0, ne); break;
     case PREAMP_WIDE: owdev::k_preamp_wide<<<per8, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, e0, ne); break;
-    case PREAMP_PAIR: owdev::k_preamp_pair<<<per64, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, e0, ne); break;
+    case PREAMP_PAIR: owdev::k_preamp_pair<<<per512, dim3(512), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, e0, ne); break;
     case PREAMP_LANE: owdev::k_preamp<<<per32, dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_sum, tsrc, p->d_pre, I, L, Lcap, e0, ne); break;
     }
     return false;
@@ -728,7 +728,7 @@ static bool launch_output_stage(ow_pool* p, const Block& b, PostKernel kernel) {
                                                                                      p->d_pa_tap, I, L, L, e0, ne, ordered ? p->d_pa_order : nullptr, p->d_pa_demand);
         return false;
     }
-    case POST_PAIR: owdev::k_post<false, true><<<dim3((ne + 63) / 64), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_pre, p->d_out, I, L, L, e0, ne, b.out_direct, b.out_stride); break;
+    case POST_PAIR: owdev::k_post<false, true><<<dim3((ne + 511) / 512), dim3(512), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_pre, p->d_out, I, L, L, e0, ne, b.out_direct, b.out_stride); break;
     case POST_OS: owdev::k_post<true><<<dim3((ne + 31) / 32), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_pre, p->d_out, I, L, L, e0, ne, b.out_direct, b.out_stride); break;
     case POST_BASE: owdev::k_post<false><<<dim3((ne + 63) / 64), dim3(64), 0, s>>>(p->dK, p->d_cs, p->d_args, p->d_eout, p->d_pre, p->d_out, I, L, L, e0, ne, b.out_direct, b.out_stride); break;
     }

@@ -12,6 +12,7 @@
 #pragma once
 #include "ow_vm.h"
 #include "ow_chain_dev.h"
+#include "ow_wave_turns.h"
 
 namespace owdev {
 
@@ -1346,14 +1347,24 @@ __global__ __launch_bounds__(64) void k_preamp(const OwConsts* __restrict__ K, d
 // the wavefronts of k_preamp: for ranges big enough to fill the chip at two per SIMD (the host's choice, `preamp_pair`).  Voice sums
 // staged in 32-sample chunks (64 rows x 33: no more LDS than k_preamp's tile).  Same operations per value: the same bits in `pre`, in
 // the state rows and in the output.
+// Workgroups of OW_TURN_WAVES = 8 wavefronts, two per SIMD, each with its own 64 engines and its own slice of the tile: the two
+// wavefronts of a SIMD sit in one workgroup and take turns by progress (ow_wave_turns.h), so that in a launch of one round -- 131 072
+// engines -- neither retires early and leaves the other to finish alone at the one-wavefront rate.  Only lanes of one wavefront
+// exchange data through the tile: wave_sync() instead of workgroup barriers; the one barrier is that of WaveTurns::init.
 #define OW_PPCHUNK 32
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
+__global__ __launch_bounds__(64 * OW_TURN_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_preamp_pair(const OwConsts* __restrict__ K, double* __restrict__ cs, const OwEngineArgs* __restrict__ args,
                    const OwEngineOut* __restrict__ eout, const double* __restrict__ sum, const OwTremSrc tsrc,
                    double* __restrict__ pre, int I, int L, int Lcap, int e0, int ne) {
-    __shared__ double tile[64 * (OW_PPCHUNK + 1)];
-    const int lane = threadIdx.x;
-    const int eb = e0 + blockIdx.x * 64;
+    __shared__ double tiles[OW_TURN_WAVES * 64 * (OW_PPCHUNK + 1)];
+    __shared__ uint32_t turn_words[OW_TURN_LDS_WORDS];
+    WaveTurns turns;
+    turns.init(turn_words);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    double* const tile = tiles + wave * (64 * (OW_PPCHUNK + 1));
+    const int lane = threadIdx.x & 63;
+    const int eb = e0 + (blockIdx.x * OW_TURN_WAVES + wave) * 64;
+    if (eb >= e0 + ne) { turns.finish(); return; }      // no engine in this wavefront
     const int e = eb + lane;
     const bool valid = e < e0 + ne;
     const int ec = valid ? e : (e0 + ne - 1);   // clamp so every lane runs the same (harmless) work
@@ -1407,8 +1418,9 @@ void k_preamp_pair(const OwConsts* __restrict__ K, double* __restrict__ cs, cons
             x = (fl & 2) ? x + b : x;
             tile[row * (OW_PPCHUNK + 1) + (lane & 31)] = x;
         }
-        __syncthreads();
+        wave_sync();
         for (int n = 0; n < cn; ++n) {
+            turns.tick((uint32_t)(base + n));
             const double x = tile[lane * (OW_PPCHUNK + 1) + n];
             const double rc[2] = {rn[0], rn[1]};
             {
@@ -1451,8 +1463,9 @@ void k_preamp_pair(const OwConsts* __restrict__ K, double* __restrict__ cs, cons
                 if (valid) pre[idx * I + e] = result;
             }
         }
-        __syncthreads();
+        wave_sync();
     }
+    turns.finish();
     if (valid) {
         dk_store(sm, cs, I, e, CS_P_MAIN);
         dk_store(ss, cs, I, e, CS_P_SHADOW);
@@ -1477,18 +1490,33 @@ void k_preamp_pair(const OwConsts* __restrict__ K, double* __restrict__ cs, cons
 // PAIR (round 6, with SPLIT = false): the oversampled chain with lane = engine -- the lane solves the two chain samples one after the
 // other and runs the half-band / speaker part ONCE: 0.83 of SPLIT's lane-work per engine, for ranges big enough to fill the chip with
 // half the wavefronts (>= 2 per SIMD: the host's choice, `post_pair`).  Same operations per value: the same bits.
+// PAIR runs in workgroups of OW_TURN_WAVES = 8 wavefronts that take turns by progress, each with its own 64 engines and its own slice
+// of the tile, as k_preamp_pair does and for the same reason; the other two forms keep their one-wavefront workgroups.
 template <bool SPLIT, bool PAIR = false>
-__global__ __launch_bounds__(64) void k_post(const OwConsts* __restrict__ K, double* __restrict__ cs, const OwEngineArgs* __restrict__ args,
-                                             OwEngineOut* __restrict__ eout, const double* __restrict__ pre, float* __restrict__ out, int I, int L,
-                                             int Lcap, int e0, int ne, float* __restrict__ out2 = nullptr, size_t ld2 = 0) {
+__global__ __launch_bounds__(64 * (PAIR ? OW_TURN_WAVES : 1))
+void k_post(const OwConsts* __restrict__ K, double* __restrict__ cs, const OwEngineArgs* __restrict__ args,
+            OwEngineOut* __restrict__ eout, const double* __restrict__ pre, float* __restrict__ out, int I, int L,
+            int Lcap, int e0, int ne, float* __restrict__ out2 = nullptr, size_t ld2 = 0) {
     // out2 / ld2: a second copy of the block, rows at stride ld2 with row 0 = engine e0 -- the caller's pinned host block, mapped into the
     // device's address space (render_range), so that no device-to-host copy trails the kernel
     constexpr int NROWS = SPLIT ? 32 : 64;
-    __shared__ float tile[NROWS * (OW_OCHUNK + 1)];
-    const int lane = threadIdx.x;
+    constexpr int W = PAIR ? OW_TURN_WAVES : 1;      // wavefronts per workgroup
+    __shared__ float tiles[W * NROWS * (OW_OCHUNK + 1)];
+    __shared__ uint32_t turn_words[PAIR ? OW_TURN_LDS_WORDS : 1];
+    WaveTurns turns;
+    int wave = 0;
+    if constexpr (PAIR) {
+        turns.init(turn_words);
+        wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    }
+    float* const tile = tiles + wave * (NROWS * (OW_OCHUNK + 1));
+    const int lane = PAIR ? (threadIdx.x & 63) : threadIdx.x;
     const int el = SPLIT ? (lane & 31) : lane;
     const int phase = SPLIT ? (lane >> 5) : 0;
-    const int eb = e0 + blockIdx.x * NROWS;
+    const int eb = e0 + (blockIdx.x * W + wave) * NROWS;
+    if constexpr (PAIR) {
+        if (eb >= e0 + ne) { turns.finish(); return; }      // no engine in this wavefront
+    }
     const int e_raw = eb + el;
     const bool valid = e_raw < e0 + ne;
     const int e = valid ? e_raw : (e0 + ne - 1);
@@ -1519,6 +1547,7 @@ __global__ __launch_bounds__(64) void k_post(const OwConsts* __restrict__ K, dou
     for (int base = 0; base < L; base += OW_OCHUNK) {
         const int cn = min(OW_OCHUNK, L - base);
         for (int n = 0; n < cn; ++n) {
+            if constexpr (PAIR) turns.tick((uint32_t)(base + n));
             const double pc = pn, pc1 = pn1;
             pn = pre[((size_t)min(base + n + 1, L - 1) * osr + phase) * I + e];
             if (PAIR) pn1 = pre[((size_t)min(base + n + 1, L - 1) * 2 + 1) * I + e];
@@ -1552,7 +1581,7 @@ __global__ __launch_bounds__(64) void k_post(const OwConsts* __restrict__ K, dou
             }
             if (phase == 0) tile[el * (OW_OCHUNK + 1) + n] = f;
         }
-        __syncthreads();
+        if constexpr (PAIR) wave_sync(); else __syncthreads();
         for (int r = 0; r < NROWS; ++r) {
             const int er = eb + r;
             if (er < e0 + ne && lane < cn) {
@@ -1561,8 +1590,9 @@ __global__ __launch_bounds__(64) void k_post(const OwConsts* __restrict__ K, dou
                 if (out2) out2[(size_t)(er - e0) * ld2 + base + lane] = f;
             }
         }
-        __syncthreads();
+        if constexpr (PAIR) wave_sync(); else __syncthreads();
     }
+    if constexpr (PAIR) turns.finish();
     if (!valid || phase != 0) return;
     if (nan_fired) {  // preamp.reset()/oversampler.reset() act on post-block state: defer the preamp/up half to k_preamp
         for (int i = 0; i < 3; ++i) { da[i] = 0.0; db[i] = 0.0; }
