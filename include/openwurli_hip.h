@@ -907,6 +907,27 @@ int ow_pump_fit(const double* r, const double* target, const uint64_t* offsets, 
                 double xatol, double fatol, uint32_t maxiter, int device, double* x_out, double* fun_out, uint32_t* nit_out, uint32_t* nfev_out,
                 uint32_t* status_out);
 
+/* ---- the pickup-law study (ml/h3_analysis_v2.py) --------------------------------------------------------------------------------- */
+/* compute_harmonics (:58-94) and its two inline variants (:291-319, :346-375) for every (carrier, law) pair of a call.  Plain scalars and
+ * pointers only (no record, no new constant).  A carrier is a row of three doubles: f0_hz, ds, vel_scale.  A law is a kind and one parameter p:
+ *   0  power   nl = y / pow(1 - y, p)                                   (the alpha sweep)
+ *   1  factor  nl = (y / (1 - y)) * (1 + p y)                           (the k list)
+ *   2  blend   nl = ((1 - p) * (y / (1 - y))) + (p * (y / (1 - y y)))   (the blend list)
+ * One job, i = 0 .. n_samples - 1: t = i / sample_rate; reed = vel_scale * sin((2 pi f0) t); y = min(max(reed * ds, -clip), clip);
+ * v = nl * sensitivity; out[i] = ((hpf_b0 v[i]) - (hpf_b0 v[i-1])) + (hpf_a1 out[i-1]) from zeros.  y_peak = max |y[i]| over
+ * i >= n_samples / 4.  With sig = out[n_samples / 2 :] of m samples and h = 1 .. n_harmonics (<= OW_MAX_HARMONICS):
+ * phase = ((2 pi (h f0)) k) / sample_rate, re = sum(sig[k] cos(phase)) / m, im = -sum(sig[k] sin(phase)) / m, amp = 2 sqrt(re re + im im).
+ * Every stated operation is one IEEE operation in that order; the sums run in ascending k (numpy's are pairwise); sin, cos and pow are the
+ * device library's, except that pow(g, 1.0) is g itself (kind 0 with p == 1 equals kind 1 with p == 0 bit for bit).  hpf_b0 / hpf_a1 are the caller's (the reference: w = tan(pi 2312 / sr), b0 = 1 / (1 + w), a1 = (1 - w) / (1 + w)).
+ * amps_out: host f64 [n_carriers][n_laws][n_harmonics]; y_peak_out: host f64 [n_carriers].  A job's numbers do not depend on the other
+ * jobs of the call, on their order or on how the laws are cut into wavefronts (by kind, at most 64 per wavefront).
+ * Returns 0, <0 on error.  Refused before any launch, the outputs untouched (ow_last_error says why): a null argument, n_samples < 4,
+ * n_harmonics of 0 or above OW_MAX_HARMONICS, a kind outside 0..2, a clip that is not inside (0, 1), any non-finite input, a sample rate
+ * that is not finite and positive.  n_carriers == 0 or n_laws == 0 returns 0 and touches nothing. */
+int ow_pickup_law(const double* carriers, size_t n_carriers, const int32_t* law_kinds, const double* law_params, size_t n_laws, double sample_rate,
+                  uint32_t n_samples, uint32_t n_harmonics, double sensitivity, double clip, double hpf_b0, double hpf_a1, int device,
+                  double* amps_out, double* y_peak_out);
+
 /* ---- recorded notes against renders (tools/wurli_compare.py) ------------------------------------------------------------------- */
 /* compute_stft (:46-58) and what its two callers take from S (harmonic_profile :61-78, measure_spectral_centroid :122-127), for many
  * clips per call.  clips: f64 [n_clips][stride] (a device pointer if clips_is_device != 0, e.g. what ow_batch_render left in HBM);

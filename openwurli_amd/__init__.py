@@ -19,6 +19,7 @@ from . import intermod_audit  # noqa: F401
 from . import overshoot  # noqa: F401
 from . import pump  # noqa: F401
 from . import pump_fit  # noqa: F401
+from . import pickup_law  # noqa: F401
 from . import bark_audit  # noqa: F401
 from . import mlp  # noqa: F401
 from .mlp import MlpWeights  # noqa: F401
@@ -28,4 +29,4 @@ from . import residuals  # noqa: F401
 from . import isolation  # noqa: F401
 from . import note_intake  # noqa: F401
 
-__all__ = ["load_library", "library_path", "OwError", "WurliEngine", "EnginePool", "VoiceState", "render_note", "batch_render", "normalize_scale", "tremolo_prefetch", "tremolo_configure", "tremolo_export", "tremolo_import", "features", "alias_audit", "midi_render", "calibrate", "preamp_bench", "render_poly", "centroid_track", "intermod_audit", "overshoot", "pump", "pump_fit", "bark_audit", "mlp", "MlpWeights", "mlp_train", "harmonics", "residuals", "isolation", "note_intake"]
+__all__ = ["load_library", "library_path", "OwError", "WurliEngine", "EnginePool", "VoiceState", "render_note", "batch_render", "normalize_scale", "tremolo_prefetch", "tremolo_configure", "tremolo_export", "tremolo_import", "features", "alias_audit", "midi_render", "calibrate", "preamp_bench", "render_poly", "centroid_track", "intermod_audit", "overshoot", "pump", "pump_fit", "pickup_law", "bark_audit", "mlp", "MlpWeights", "mlp_train", "harmonics", "residuals", "isolation", "note_intake"]

@@ -443,6 +443,8 @@ SYMBOLS = {
     "ow_pump_fit_eval": (C.c_int, [_VP, _VP, _VP, _VP, C.c_size_t, _VP, _VP, C.c_size_t, _VP, _VP, _VP, C.c_size_t, C.c_uint32, C.c_int, _VP, _VP, C.c_size_t]),
     "ow_pump_fit": (C.c_int, [_VP, _VP, _VP, _VP, C.c_size_t, _VP, _VP, C.c_size_t, _VP, _VP, _VP, C.c_size_t, C.c_uint32, C.c_double, C.c_double,
                               C.c_uint32, C.c_int, _VP, _VP, _VP, _VP, _VP]),
+    "ow_pickup_law": (C.c_int, [_VP, C.c_size_t, _VP, _VP, C.c_size_t, C.c_double, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                C.c_int, _VP, _VP]),
     "ow_stft_profile": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, _VP, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int, C.c_int, _VP, _VP]),
     "ow_frame_rms": (C.c_int, [_VP, C.c_size_t, C.c_size_t, _VP, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP, _VP]),
 }

@@ -50,6 +50,7 @@
 #include "ow_bark_kernels.h"
 #include "ow_pump_kernels.h"
 #include "ow_pump_fit_kernels.h"
+#include "ow_pickup_law_kernels.h"
 #include "ow_midi_kernels.h"
 #include "ow_chain_wide.h"
 #include "ow_chain_stream.h"
@@ -87,6 +88,7 @@ using owdev::OwEngineOut;
 #include "host/api_bark_audit.inc"      // C-ABI: `preamp-bench bark-audit` (H2 / H1 per chain stage, many notes per call)
 #include "host/api_pump.inc"            // C-ABI: `preamp-bench pump-sweep` / `pump-trace` / `pump-spike` / `pump-step` / `pump-sinusoid` (the pump measurements)
 #include "host/api_pump_fit.inc"        // C-ABI: tools/analyze_pump_dynamics.py (six IIR predictors of the pump, their RMSE, Nelder-Mead; many fits per call)
+#include "host/api_pickup_law.inc"     // C-ABI: ml/h3_analysis_v2.py (the pickup-law study: every law point of every carrier per call)
 #include "host/api_harmonics.inc"       // C-ABI: the recording side of the ML loop (Goertzel harmonics, inter-harmonic noise floor; many segments per call)
 #include "host/api_compare.inc"         // C-ABI: the analysis of tools/wurli_compare.py (LDS FFT: mean spectrum and centroid of many clips per call; RMS envelopes)
 #include "host/api_isolation.inc"       // C-ABI: recorded-note intake (isolation sub-scores of all notes of all files per call, clip bounds of many clips per call)
